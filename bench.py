@@ -14,6 +14,11 @@ data-path collective ("scaling": "weak"); only the timing (max over ranks)
 and the 3 error counters are reduced after the timed region.
 
 Prints ONE JSON line on rank 0 (contract in the task statement / DESIGN.md).
+
+A plain run sets up, warms up, times --steps steps, writes the last step's
+outputs when --dump-outputs is given and prints the line.  The CPU baselines
+(the reference's SSE decoder and the product's host decoder, seconds each) run
+only with --full.
 """
 import argparse
 import json
@@ -51,7 +56,14 @@ def parse():
     ap.add_argument("--kernel", type=int, default=0,
                     help="0 auto, 1 generic, 2 windowed, 3 windowed2 S=16, 5 coop, 7 lds, 8 coop3, 9 ldsep (float)")
     ap.add_argument("--seed", type=int, default=2024)
-    ap.add_argument("--cpu-seconds", type=float, default=8.0, help="CPU baseline time budget (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also time the CPU baselines (--cpu-seconds); a plain run "
+                         "reports cpu_baseline null")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last step left (hard decisions, error counters, "
+                         "iterations used) as DIR/<name>.npy, float32 / float64; rank 0's shard only")
+    ap.add_argument("--cpu-seconds", type=float, default=8.0,
+                    help="CPU baseline time budget with --full (0 = skip)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = this process's CPU share (cgroup quota / affinity)")
     ap.add_argument("--traffic-file", default=os.path.join(ROOT, "profiles", "traffic.json"))
     a = ap.parse_args()
@@ -64,7 +76,33 @@ def parse():
         a.iters = 20 if f32 else 50
     if a.steps is None:
         a.steps = 400 if f32 and not a.mixed else 10
+    if not a.full:
+        a.cpu_seconds = 0.0
     return a
+
+
+DUMP_HARD_BYTES = 48 << 20   # float32 bytes of hard decisions written by --dump-outputs (64 MB in all)
+
+
+def dump_outputs(path, hard, extra):
+    """--dump-outputs: the arrays the last timed step left in the caller's
+    buffers.  `hard` (uint8 [B, N] on the device) is written whole as float32
+    when that fits DUMP_HARD_BYTES, else as a fixed seeded sample of whole
+    codewords (hard_rows: their indices); hard_weight (ones per codeword)
+    covers every codeword either way.  `extra`: name -> small array."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    B, N = hard.shape
+    keep = max(1, DUMP_HARD_BYTES // (4 * N))
+    rows = np.arange(B) if B <= keep else np.sort(np.random.default_rng(0).choice(B, keep, replace=False))
+    out = dict(extra)
+    out["hard"] = hard[torch.from_numpy(rows).to(hard.device)].cpu().numpy().astype(np.float32)
+    out["hard_rows"] = rows
+    out["hard_weight"] = hard.sum(dim=1, dtype=torch.int64).cpu().numpy()
+    for name, arr in out.items():
+        arr = np.asarray(arr)
+        np.save(os.path.join(path, name + ".npy"), arr if arr.dtype == np.float32 else arr.astype(np.float64))
 
 
 def hbm_peak_gbs():
@@ -352,6 +390,8 @@ def bench_mixed(a, rank, world, local, torch, dist):
     kt = mx.kernel_time(reset=True)
     mx.profile(False)
     h, it = hard.cpu().numpy(), its.cpu().numpy()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, hard, {"iters_used": it})
     # per rate over ALL ranks: frames, bit errors, frame errors, iterations,
     # algorithmic bytes (sums) and the decode launch time (max)
     sums = []
@@ -548,6 +588,9 @@ def main():
         kms, launches = ev0.elapsed_time(ev1), a.steps
 
     be_l, fe_l = counts.tolist()
+    if a.dump_outputs and rank == 0:
+        # counts: the caller's accumulator after the timed steps (every step adds its bit and frame errors)
+        dump_outputs(a.dump_outputs, hard, {"counts": np.array([be_l, fe_l])})
     el, be, fe, _ = reduce_results(el, be_l, fe_l, B * a.steps, device="cuda")
     kernel_ms, _, _, _ = reduce_results(kms / max(launches, 1), 0, 0, 0, device="cuda")
     per_rank = rank_list({"device": local, "kernel_ms": round(kms / max(launches, 1), 4),

@@ -37,10 +37,10 @@ for s in ${STEPS:-smoke tests bench}; do
     smoke) step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
     tests) step tests 1100 python -u -m pytest ${PYTEST_FILES:-tests} -m gpu -x -q -p no:cacheprovider --timeout 200 \
                --timeout-method thread ${PYTEST_K:+-k "$PYTEST_K"} ;;
-    bench) step bench 300 python bench.py ${BENCH_ARGS:-} ;;
-    f32) step f32 300 python bench.py --dtype f32 ${BENCH_ARGS:-} ;;
-    mixed) step mixed 300 python bench.py --mixed ${BENCH_ARGS:-} ;;
-    mixed24k) step mixed24k 400 python bench.py --mixed --batch 24576 --steps 3 --warmup 1 ${BENCH_ARGS:-} ;;
+    bench) step bench 300 python bench.py --full ${BENCH_ARGS:-} ;;
+    f32) step f32 300 python bench.py --full --dtype f32 ${BENCH_ARGS:-} ;;
+    mixed) step mixed 300 python bench.py --full --mixed ${BENCH_ARGS:-} ;;
+    mixed24k) step mixed24k 400 python bench.py --full --mixed --batch 24576 --steps 3 --warmup 1 ${BENCH_ARGS:-} ;;
     mixedref) step mixedref 300 python bench.py --mixed --mixed-codes reference --cpu-seconds 0 ;;
     codes) for c in $CODES; do
                step "code_${c%%:*}" 200 python bench.py --code ${c%%:*} --ebn0 ${c##*:} --steps 5 --warmup 1 --cpu-seconds 0
