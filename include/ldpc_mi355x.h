@@ -43,6 +43,11 @@
  *          on-GPU channel (code/gpu_fixed/awgn_channel/CChanel_AWGN_SIMD.cu:7-30)
  *   ldpc_count_errors_async -> CErrorAnalyzer::generate
  *          (code/x86/CErrorAnalyzer/CErrorAnalyzer.cpp:123-154)
+ *   ldpc_info_bits_host / _async -> CBitGenerator::generate (rand() % 2 per
+ *          information bit, called per frame at code/x86/main_p.cpp:431-445),
+ *          with a counter-based generator indexed per codeword
+ *   ldpc_dvbs2_encode / _async -> GenericEncoder::encode
+ *          (code/x86/CEncoder/GenericEncoder.cpp:38-78)
  *
  * Threading: a ldpc_code is immutable and may be shared by any number of
  * contexts/threads.  A ldpc_ctx owns device scratch and is not re-entrant
@@ -290,6 +295,25 @@ int ldpc_mixed_kernel_time(ldpc_mixed *mx, int code_index, double *total_ms, int
  * reference's GenericEncoder::encode (code/x86/CEncoder/GenericEncoder.cpp:38-78):
  * info [batch][K] 0/1 -> codeword [batch][N] = [info, parity]. */
 int ldpc_dvbs2_encode(const ldpc_code *h, const uint8_t *info, uint8_t *codeword, int batch);
+/* Device twin of ldpc_dvbs2_encode, asynchronous on hip_stream (NULL: the null
+ * stream): d_info [batch][K] -> d_codeword [batch][N] = [info & 1, parity],
+ * byte-equal to the host encoder.  One workgroup per codeword, the codeword
+ * held in LDS: no scratch, no allocation, no synchronisation, and batch is not
+ * limited by the context's max_batch.  d_info and d_codeword must not overlap.
+ * LDPC_EUNSUPPORTED for a code not built from an Annex-B table, or one whose
+ * N bytes do not fit a workgroup's 64 KiB of LDS. */
+int ldpc_dvbs2_encode_async(ldpc_ctx *ctx, void *hip_stream, const uint8_t *d_info,
+                            uint8_t *d_codeword, int batch);
+
+/* ---- bit source ----------------------------------------------------------- */
+/* info[b][i] = bit 63 of splitmix64(((first_cw + b) * K + i) ^ (seed * 0xA0761D6478BD642FULL)),
+ * the splitmix64 of the channel below under another key multiplier, so the
+ * bits and the noise of one seed are separate streams.  Indexed per codeword
+ * like the channel: any shard, any first_cw draws the same bits.
+ * _async: K = n - m of ctx's code, device buffer [batch][K]. */
+int ldpc_info_bits_host (int k, int batch, uint64_t first_cw, uint64_t seed, uint8_t *info);
+int ldpc_info_bits_async(ldpc_ctx *ctx, void *hip_stream, uint8_t *d_info, int batch,
+                         uint64_t first_cw, uint64_t seed);
 
 /* ---- synthetic channel -------------------------------------------------- */
 /* sigma = sqrt(10^(-(EbN0 + 10 log10(rate))/10) / 2)  (CChanelAWGN_MKL.cpp:102-105) */

@@ -103,6 +103,9 @@ SIGNATURES = {
     "ldpc_mixed_profile": (I, [P, I]),
     "ldpc_mixed_kernel_time": (I, [P, I, C.POINTER(C.c_double), C.POINTER(I), I]),
     "ldpc_dvbs2_encode": (I, [P, P, P, I]),
+    "ldpc_dvbs2_encode_async": (I, [P, P, P, P, I]),
+    "ldpc_info_bits_host": (I, [I, I, U64, U64, P]),
+    "ldpc_info_bits_async": (I, [P, P, P, I, U64, U64]),
     "ldpc_awgn_sigma": (C.c_double, [C.c_double, C.c_double]),
     "ldpc_awgn_i8_table": (I, [C.c_double, I, I, P]),
     "ldpc_awgn_sigma_ex": (C.c_double, [C.c_double, C.c_double, I]),

@@ -48,6 +48,15 @@ def i8_table(sigma, factor=8, sat=31, amp=BPSK, normalize=False):
     return t
 
 
+def info_bits_host(k, batch, seed, first_cw=0):
+    """Information bits [batch, k] of codewords first_cw .. (``ldpc_info_bits_host``,
+    bit-equal to ``Decoder.info_bits_device``):
+    bit 63 of splitmix64((cw*k + i) ^ (seed * 0xA0761D6478BD642F))."""
+    out = np.empty((batch, k), dtype=np.uint8)
+    _lib.check(_lib.lib().ldpc_info_bits_host(k, batch, first_cw, seed, out.ctypes.data))
+    return out
+
+
 def awgn_i8_host(n, batch, seed, table, first_cw=0, codeword=None):
     out = np.empty((batch, n), dtype=np.int8)
     cw = None

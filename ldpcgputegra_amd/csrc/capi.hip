@@ -22,6 +22,7 @@
 #include "coop.h"
 #include "stairf.h"
 #include "lds.h"
+#include "encode.h"
 #include "host.h"
 
 #define HIP_TRY(expr)                                                                          \
@@ -84,6 +85,7 @@ struct ldpc_ctx {
     CoopCode coop3{};               // coop3.hip tables (pre + post slab waves, i16 chain, D0 = 7)
     LdsCode lds{};                  // lds.hip tables (LDS-resident short-code decoder)
     StairfCode stairf{};            // stairf.hip table (float staircase codes)
+    EncodeCode enc{};               // encode.hip table (DVB-S2 IRA encoder)
     Scratch sc;                     // device-API decodes and the unchunked host path
     void *d_io = nullptr;           // staging for the quantiser's host-buffer API
     size_t io_bytes = 0;
@@ -187,6 +189,7 @@ extern "C" int ldpc_ctx_create(const ldpc_code *h, int device, int max_batch, ld
     if ((rc = coop3_upload(h, &c->coop3)) != LDPC_OK) return fail(rc);
     if ((rc = lds_upload(h, &c->lds)) != LDPC_OK) return fail(rc);
     if ((rc = stairf_upload(h, &c->stairf)) != LDPC_OK) return fail(rc);
+    if ((rc = encode_upload(h, &c->enc)) != LDPC_OK) return fail(rc);
     *out = c;
     return LDPC_OK;
 }
@@ -208,6 +211,7 @@ extern "C" void ldpc_ctx_destroy(ldpc_ctx *c)
     coop_free(&c->coop3);
     lds_free(&c->lds);
     stairf_free(&c->stairf);
+    encode_free(&c->enc);
     for (auto &pr : c->events) {
         (void)hipEventDestroy(pr.first);
         (void)hipEventDestroy(pr.second);
@@ -871,6 +875,40 @@ extern "C" int ldpc_awgn_i8_async(ldpc_ctx *c, void *s, int8_t *d_llr, int batch
     memcpy(t.t, table, sizeof(t.t));
     if (launch_awgn_i8(d_llr, c->code->n, batch, first_cw, seed, t, d_codeword, (hipStream_t)s))
         return ldpc_set_error(LDPC_EDEVICE, "awgn: %s", hipGetErrorString(hipGetLastError()));
+    return LDPC_OK;
+}
+
+// the bit source of the chain (the reference's CBitGenerator::generate): K = n - m bits per codeword
+extern "C" int ldpc_info_bits_async(ldpc_ctx *c, void *s, uint8_t *d_info, int batch, uint64_t first_cw,
+                                    uint64_t seed)
+{
+    if (!c || batch < 0 || (batch > 0 && !d_info)) return ldpc_set_error(LDPC_EINVAL, "info_bits args");
+    if (c->device < 0) return host_only(c);
+    if (batch == 0) return LDPC_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    if (launch_info_bits(d_info, c->code->n - c->code->m, batch, first_cw, seed, (hipStream_t)s))
+        return ldpc_set_error(LDPC_EDEVICE, "info_bits: %s", hipGetErrorString(hipGetLastError()));
+    return LDPC_OK;
+}
+
+// device twin of ldpc_dvbs2_encode (code.cpp): no scratch, so any batch
+extern "C" int ldpc_dvbs2_encode_async(ldpc_ctx *c, void *s, const uint8_t *d_info, uint8_t *d_codeword, int batch)
+{
+    if (!c || batch < 0 || (batch > 0 && (!d_info || !d_codeword)))
+        return ldpc_set_error(LDPC_EINVAL, "encode args");
+    if (c->device < 0) return host_only(c);
+    const ldpc_code *h = c->code;
+    if (h->dvbs2_q <= 0) return ldpc_set_error(LDPC_EUNSUPPORTED, "code was not built from a DVB-S2 table");
+    if (!c->enc.valid)
+        return ldpc_set_error(LDPC_EUNSUPPORTED, "encoder: a codeword of n = %d needs %zu B of LDS, one workgroup "
+                              "has %zu", h->n, encode_lds_bytes(h->n - h->m, h->m), kEncMaxLds);
+    if (batch == 0) return LDPC_OK;
+    const uintptr_t i0 = (uintptr_t)d_info, c0 = (uintptr_t)d_codeword;
+    if (i0 < c0 + (size_t)batch * h->n && c0 < i0 + (size_t)batch * (h->n - h->m))
+        return ldpc_set_error(LDPC_EINVAL, "encode: d_info and d_codeword overlap");
+    HIP_TRY(hipSetDevice(c->device));
+    if (launch_dvbs2_encode(c->enc, d_info, d_codeword, batch, (hipStream_t)s))
+        return ldpc_set_error(LDPC_EDEVICE, "encode: %s", hipGetErrorString(hipGetLastError()));
     return LDPC_OK;
 }
 

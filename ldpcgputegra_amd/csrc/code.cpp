@@ -412,6 +412,20 @@ static inline uint64_t splitmix64(uint64_t x)
     return x ^ (x >> 31);
 }
 
+// The chain's bit source (device twin: info_bits_k, encode.hip), where the
+// reference draws rand() % 2 (CBitGenerator::generate): bit i of codeword cw is
+// the top bit of splitmix64((cw*K + i) ^ (seed * 0xA0761D6478BD642F)) -- indexed
+// per codeword like the channel, keyed apart from it.
+extern "C" int ldpc_info_bits_host(int k, int batch, uint64_t first_cw, uint64_t seed, uint8_t *info)
+{
+    if (k <= 0 || batch < 0 || (batch > 0 && !info)) return ldpc_set_error(LDPC_EINVAL, "info_bits host args");
+    const uint64_t key = seed * 0xA0761D6478BD642Full;
+    for (int b = 0; b < batch; b++)
+        for (int i = 0; i < k; i++)
+            info[(size_t)b * k + i] = (uint8_t)(splitmix64(((first_cw + b) * (uint64_t)k + i) ^ key) >> 63);
+    return LDPC_OK;
+}
+
 // Generator definition (also implemented by the HIP kernel in decode.hip and
 // by tests/golden/gen_golden.py): element idx = cw*N + i,
 //   u = splitmix64(idx ^ (seed * 0xD1B54A32D192ED03)) >> 32

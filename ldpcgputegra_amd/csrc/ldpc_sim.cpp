@@ -10,7 +10,12 @@
 //
 //   ldpc_sim -code dvbs2_r1_2 -min 0.8 -max 1.2 -pas 0.1 -iter 50 -fer 100
 //            [-batch 4096] [-frames 1000000] [-OMS 1 | -NMS 29 | -MS]
-//            [-encoder] [-et] [-gpus N] [-seed S] [-kernel K]
+//            [-encoder [-fresh]] [-et] [-gpus N] [-seed S] [-kernel K]
+//
+// -encoder alone draws 64 codewords once on the host and replicates them over
+// every batch; -encoder -fresh draws new information bits and encodes them on
+// the GPU for every frame, as the reference's chain does per frame
+// (code/x86/main_p.cpp:431-445, 490-498).
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -33,7 +38,7 @@ struct Opt {
     double min = 0.5, max = 3.0, pas = 0.1;
     int iter = 30, fer = 100, batch = 4096, gpus = 1, kernel = 0;
     long frames = 1 << 20;
-    bool encoder = false;
+    bool encoder = false, fresh = false;
     ldpc_params p{};
     uint64_t seed = 1;
 };
@@ -85,7 +90,14 @@ void worker(int dev, const ldpc_code *h, const Opt &o, double sigma, Totals &tot
         fprintf(stderr, "hipMalloc failed\n");
         exit(1);
     }
-    if (o.encoder) {
+    uint8_t *d_info = nullptr;
+    if (o.fresh) {
+        // bits and codewords are drawn on the device per batch: no pool, no upload
+        if (hipMalloc(&d_info, (size_t)o.batch * k) || hipMalloc(&d_cw, (size_t)o.batch * n)) {
+            fprintf(stderr, "hipMalloc failed\n");
+            exit(1);
+        }
+    } else if (o.encoder) {
         // the codeword pool replicated over the batch (noise differs per codeword)
         std::vector<uint8_t> rep((size_t)o.batch * n);
         for (int b = 0; b < o.batch; b++) memcpy(&rep[(size_t)b * n], &pool[(size_t)(b % pool_n) * n], n);
@@ -98,6 +110,10 @@ void worker(int dev, const ldpc_code *h, const Opt &o, double sigma, Totals &tot
         if (tot.fe.load() >= o.fer || tot.frames.load() >= o.frames) break;
         const uint64_t first = (uint64_t)batch_no * o.batch;
         (void)hipMemsetAsync(d_cnt, 0, 16, (hipStream_t)stream);
+        if (o.fresh) {
+            CHECK(ldpc_info_bits_async(ctx, stream, d_info, o.batch, first, o.seed));
+            CHECK(ldpc_dvbs2_encode_async(ctx, stream, d_info, d_cw, o.batch));
+        }
         CHECK(ldpc_awgn_i8_async(ctx, stream, d_llr, o.batch, first, o.seed, table, d_cw));
         CHECK(ldpc_decode_i8_async(ctx, stream, d_llr, d_hard, nullptr, nullptr, o.batch, o.iter, &o.p));
         CHECK(ldpc_count_errors_async(ctx, stream, d_hard, o.batch, k, d_cw, d_cnt));
@@ -115,6 +131,7 @@ void worker(int dev, const ldpc_code *h, const Opt &o, double sigma, Totals &tot
     (void)hipFree(d_hard);
     (void)hipFree(d_cnt);
     if (d_cw) (void)hipFree(d_cw);
+    if (d_info) (void)hipFree(d_info);
     ldpc_ctx_destroy(ctx);
 }
 
@@ -142,11 +159,16 @@ int main(int argc, char **argv)
         else if (a == "-NMS") { o.p.algo = LDPC_ALGO_NMS; o.p.factor = atoi(nxt()); }
         else if (a == "-MS") o.p.algo = LDPC_ALGO_MS;
         else if (a == "-encoder") o.encoder = true;
+        else if (a == "-fresh") o.fresh = true;
         else if (a == "-et") o.p.early_term = 1;
         else {
             fprintf(stderr, "unknown option %s\n", a.c_str());
             return 2;
         }
+    }
+    if (o.fresh && !o.encoder) {
+        fprintf(stderr, "usage: -fresh (new codewords every frame) needs -encoder\n");
+        return 2;
     }
     ldpc_code *h;
     CHECK(ldpc_code_load(code_path(o.code, argv[0]).c_str(), &h));
@@ -161,7 +183,9 @@ int main(int argc, char **argv)
     }
     std::vector<uint8_t> pool;
     int pool_n = 0;
-    if (o.encoder) {
+    if (o.fresh) {
+        CHECK(ldpc_dvbs2_encode(h, nullptr, nullptr, 0));   // the library's verdict on the code, before any GPU work
+    } else if (o.encoder) {
         pool_n = 64;
         std::vector<uint8_t> info((size_t)pool_n * k);
         std::mt19937_64 rng(o.seed);

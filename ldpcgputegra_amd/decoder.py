@@ -203,6 +203,22 @@ class Decoder:
         self._on_stream(stream, lambda s: _lib.check(_lib.lib().ldpc_awgn_i8_async(
             self._ctx, s, self._ptr(llr), llr.shape[0], first_cw, seed, t.ctypes.data, self._ptr(codeword))), self.device)
 
+    def info_bits_device(self, info, first_cw, seed, stream=None):
+        """Fill info (uint8 [batch, K]) with the information bits of codewords
+        first_cw .. (channel.info_bits_host's generator, on the device)."""
+        assert info.is_contiguous() and info.numel() == info.shape[0] * self.code.k_info
+        self._on_stream(stream, lambda s: _lib.check(_lib.lib().ldpc_info_bits_async(
+            self._ctx, s, self._ptr(info), info.shape[0], first_cw, seed)), self.device)
+
+    def encode_device(self, info, codeword, stream=None):
+        """DVB-S2 IRA encoding on the device: info uint8 [batch, K] (taken & 1)
+        -> codeword uint8 [batch, N] = [info, parity], byte-equal to Code.encode."""
+        B = info.shape[0]
+        assert info.is_contiguous() and info.numel() == B * self.code.k_info
+        assert codeword.is_contiguous() and codeword.numel() == B * self.code.n
+        self._on_stream(stream, lambda s: _lib.check(_lib.lib().ldpc_dvbs2_encode_async(
+            self._ctx, s, self._ptr(info), self._ptr(codeword), B)), self.device)
+
     def quantize_device(self, y, q, factor=8, sat_neg=-31, sat_pos=31, stream=None):
         """float -> int8 LLR on the device (CFastFixConversion::generate's rule:
         clamp(trunc(factor * y), sat_neg, sat_pos)); y float32, q int8, same numel."""
