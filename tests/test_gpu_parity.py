@@ -30,10 +30,12 @@ def decoder(code, kernel=0, max_batch=4096):
 
 
 def kernels_for(code):
-    """Kernel families that can run this code: 1 generic, 2 windowed,
-    3 windowed2 (S=16), 5 coop (workgroup-cooperative), 7 lds (LDS-resident
-    short codes), 8 coop3 (slab waves doing pre + post, i16 chain; first-group
-    degree 7 or 10).  (4 = windowed2 S=32 and 6 = coop2 were superseded and removed.)"""
+    """Kernel families that can run this code: 1 generic, 2 windowed
+    (staircase codes of first-group degree 7 or 10), 3 windowed2 (S=16;
+    degrees 7, 10, 14, 22, 27, 30), 5 coop (workgroup-cooperative; degrees 7,
+    10, 14, 22), 7 lds (LDS-resident short codes), 8 coop3 (slab waves doing
+    pre + post, i16 chain; degrees 7, 10, 14, 22, 27, 30).  (4 = windowed2
+    S=32 and 6 = coop2 were superseded and removed.)"""
     ks = [1]
     c = Code(code)
     if c.plan_info()["windowed"]:
