@@ -48,6 +48,8 @@
  *          with a counter-based generator indexed per codeword
  *   ldpc_dvbs2_encode / _async -> GenericEncoder::encode
  *          (code/x86/CEncoder/GenericEncoder.cpp:38-78)
+ *   ldpc_encoder_* / ldpc_encode / _async -> nothing: the reference encodes
+ *          IRA codes only; these encode every ldpc_code
  *
  * Threading: a ldpc_code is immutable and may be shared by any number of
  * contexts/threads.  A ldpc_ctx owns device scratch and is not re-entrant
@@ -304,6 +306,49 @@ int ldpc_dvbs2_encode(const ldpc_code *h, const uint8_t *info, uint8_t *codeword
  * N bytes do not fit a workgroup's 64 KiB of LDS. */
 int ldpc_dvbs2_encode_async(ldpc_ctx *ctx, void *hip_stream, const uint8_t *d_info,
                             uint8_t *d_codeword, int batch);
+
+/* ---- general encoder ---------------------------------------------------- */
+/* An encoder for any ldpc_code (the reference has none for codes that are not
+ * IRA).  ldpc_encoder_create reduces H over GF(2), bit-packed; the result is
+ * canonical, whatever the order of elimination:
+ *   parity positions: scanning columns N-1 .. 0, a column is a parity position
+ *     iff it is linearly independent of the parity columns chosen before it;
+ *     their count is rank (<= M);
+ *   information positions: the K = N - M lowest remaining columns, ascending;
+ *   forced zeros: the other M - rank remaining columns (only when rank < M);
+ *   systematic = 1 iff the information positions are 0 .. K-1: the codeword
+ *     is then [info, parity], the layout of ldpc_dvbs2_encode;
+ *   the parity bits are the unique solution of H x = 0 given the others.
+ * A code built from an Annex-B table has its staircase columns K .. N-1 as
+ * parity positions: no elimination, ldpc_encode / ldpc_encode_async run the
+ * IRA encoders above and are byte-equal to them.  For any other code the
+ * dense M x N bit matrix (M * ceil(N / 64) * 8 bytes) must fit 64 MiB, else
+ * LDPC_EUNSUPPORTED -- every shipped table does (20000x10000: 25 MB; its
+ * elimination takes seconds).
+ * The encoder is immutable and may be shared by contexts and threads; the code
+ * it was built from must outlive it. */
+typedef struct ldpc_encoder ldpc_encoder;
+int ldpc_encoder_create(const ldpc_code *h, ldpc_encoder **out);
+void ldpc_encoder_destroy(ldpc_encoder *e);
+/* any of n, k, rank, systematic may be NULL */
+int ldpc_encoder_info(const ldpc_encoder *e, int *n, int *k, int *rank, int *systematic);
+/* info_pos [k], parity_pos [rank], ascending; either may be NULL */
+int ldpc_encoder_positions(const ldpc_encoder *e, int32_t *info_pos, int32_t *parity_pos);
+/* Host: info [batch][K] (info & 1 is taken) -> codeword [batch][N], every byte
+ * written 0 / 1: codeword[info_pos[i]] = info[i], the parity bits at
+ * parity_pos, 0 at the forced positions. */
+int ldpc_encode(const ldpc_encoder *e, const uint8_t *info, uint8_t *codeword, int batch);
+/* Attach an encoder of the context's code to a GPU context: uploads its
+ * matrix (synchronous, allocates device memory; replaces an earlier one after
+ * waiting for the device).  LDPC_EINVAL for an encoder of another code,
+ * LDPC_EUNSUPPORTED for a host context. */
+int ldpc_ctx_set_encoder(ldpc_ctx *ctx, const ldpc_encoder *e);
+/* Device twin of ldpc_encode with the conventions of ldpc_dvbs2_encode_async:
+ * asynchronous on hip_stream (NULL: the null stream), byte-equal to the host
+ * encoder, no allocation, no synchronisation, batch not limited by max_batch,
+ * batch = 0 is LDPC_OK, overlapping buffers LDPC_EINVAL, a host context
+ * LDPC_EUNSUPPORTED, a context without an attached encoder LDPC_EINVAL. */
+int ldpc_encode_async(ldpc_ctx *ctx, void *hip_stream, const uint8_t *d_info, uint8_t *d_codeword, int batch);
 
 /* ---- bit source ----------------------------------------------------------- */
 /* info[b][i] = bit 63 of splitmix64(((first_cw + b) * K + i) ^ (seed * 0xA0761D6478BD642FULL)),

@@ -7,12 +7,12 @@ include/ldpc_mi355x.h); this package is its host-side binding.
 """
 from . import _lib
 from ._lib import ALGO_MS, ALGO_NMS, ALGO_OMS, LdpcError, default_params
-from .codes import Code, Table, available, load_table
+from .codes import Code, Encoder, Table, available, load_table
 from .decoder import (CDecoder, CDecoder_NMS_fixed_MI355X, CDecoder_OMS_fixed_MI355X, CreateDecoder, Decoder,
                       param_decoder, pinned_empty)
 
 __all__ = [
-    "ALGO_MS", "ALGO_NMS", "ALGO_OMS", "LdpcError", "default_params", "Code", "Table", "available",
+    "ALGO_MS", "ALGO_NMS", "ALGO_OMS", "LdpcError", "default_params", "Code", "Encoder", "Table", "available",
     "load_table", "CDecoder", "CDecoder_OMS_fixed_MI355X", "CDecoder_NMS_fixed_MI355X", "CreateDecoder",
     "Decoder", "param_decoder", "pinned_empty",
 ]

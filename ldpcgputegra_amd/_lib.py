@@ -104,6 +104,13 @@ SIGNATURES = {
     "ldpc_mixed_kernel_time": (I, [P, I, C.POINTER(C.c_double), C.POINTER(I), I]),
     "ldpc_dvbs2_encode": (I, [P, P, P, I]),
     "ldpc_dvbs2_encode_async": (I, [P, P, P, P, I]),
+    "ldpc_encoder_create": (I, [P, C.POINTER(P)]),
+    "ldpc_encoder_destroy": (None, [P]),
+    "ldpc_encoder_info": (I, [P, C.POINTER(I), C.POINTER(I), C.POINTER(I), C.POINTER(I)]),
+    "ldpc_encoder_positions": (I, [P, P, P]),
+    "ldpc_encode": (I, [P, P, P, I]),
+    "ldpc_ctx_set_encoder": (I, [P, P]),
+    "ldpc_encode_async": (I, [P, P, P, P, I]),
     "ldpc_info_bits_host": (I, [I, I, U64, U64, P]),
     "ldpc_info_bits_async": (I, [P, P, P, I, U64, U64]),
     "ldpc_awgn_sigma": (C.c_double, [C.c_double, C.c_double]),

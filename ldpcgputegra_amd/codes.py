@@ -196,6 +196,12 @@ class Code:
         _lib.check(_lib.lib().ldpc_dvbs2_encode(self._h, info.ctypes.data, cw.ctypes.data, info.shape[0]))
         return cw
 
+    def encoder(self):
+        """General GF(2) encoder of this code (any code; an Annex-B code's
+        delegates to the IRA encoder).  Built by elimination: seconds for the
+        largest tables."""
+        return Encoder(self)
+
     def window_plan(self, S, P):
         """[(first check, count)] of the windowed2 schedule (empty if none)."""
         L = _lib.lib()
@@ -246,4 +252,42 @@ class Code:
         h = getattr(self, "_h", None)
         if h is not None and _lib._lib is not None:
             _lib._lib.ldpc_code_destroy(h)
+            self._h = None
+
+
+class Encoder:
+    """C-ABI ``ldpc_encoder`` handle: immutable, shareable across contexts.
+
+    ``info_pos`` [K] / ``parity_pos`` [rank]: ascending codeword positions of
+    the information / parity bits (the M - rank other positions are always 0);
+    ``systematic``: info_pos == 0 .. K-1, the codeword is [info, parity]."""
+
+    def __init__(self, code):
+        self.code = code if isinstance(code, Code) else Code(code)   # kept alive: the encoder refers to it
+        L = _lib.lib()
+        h = C.c_void_p()
+        _lib.check(L.ldpc_encoder_create(self.code.handle, C.byref(h)))
+        self._h = h
+        n, k, r, s = (C.c_int() for _ in range(4))
+        _lib.check(L.ldpc_encoder_info(h, C.byref(n), C.byref(k), C.byref(r), C.byref(s)))
+        self.n, self.k, self.rank, self.systematic = n.value, k.value, r.value, bool(s.value)
+        self.info_pos = np.empty(self.k, dtype=np.int32)
+        self.parity_pos = np.empty(self.rank, dtype=np.int32)
+        _lib.check(L.ldpc_encoder_positions(h, self.info_pos.ctypes.data, self.parity_pos.ctypes.data))
+
+    @property
+    def handle(self):
+        return self._h
+
+    def encode(self, info):
+        """info bits [batch, K] (taken & 1) -> codewords uint8 [batch, N] on the host."""
+        info = np.ascontiguousarray(info, dtype=np.uint8).reshape(-1, self.k)
+        cw = np.empty((info.shape[0], self.n), dtype=np.uint8)
+        _lib.check(_lib.lib().ldpc_encode(self._h, info.ctypes.data, cw.ctypes.data, info.shape[0]))
+        return cw
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and _lib._lib is not None:
+            _lib._lib.ldpc_encoder_destroy(h)
             self._h = None

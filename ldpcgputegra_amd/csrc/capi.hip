@@ -23,6 +23,7 @@
 #include "stairf.h"
 #include "lds.h"
 #include "encode.h"
+#include "genc_dev.h"
 #include "host.h"
 
 #define HIP_TRY(expr)                                                                          \
@@ -86,6 +87,9 @@ struct ldpc_ctx {
     LdsCode lds{};                  // lds.hip tables (LDS-resident short-code decoder)
     StairfCode stairf{};            // stairf.hip table (float staircase codes)
     EncodeCode enc{};               // encode.hip table (DVB-S2 IRA encoder)
+    bool genc_attached = false;     // ldpc_ctx_set_encoder: an encoder of this code is attached
+    bool genc_ira = false;          // ... which delegates to enc (Annex-B code), else:
+    GencDev genc{};                 // genc.hip copy of the attached general encoder
     Scratch sc;                     // device-API decodes and the unchunked host path
     void *d_io = nullptr;           // staging for the quantiser's host-buffer API
     size_t io_bytes = 0;
@@ -212,6 +216,7 @@ extern "C" void ldpc_ctx_destroy(ldpc_ctx *c)
     lds_free(&c->lds);
     stairf_free(&c->stairf);
     encode_free(&c->enc);
+    genc_free(&c->genc);
     for (auto &pr : c->events) {
         (void)hipEventDestroy(pr.first);
         (void)hipEventDestroy(pr.second);
@@ -908,6 +913,51 @@ extern "C" int ldpc_dvbs2_encode_async(ldpc_ctx *c, void *s, const uint8_t *d_in
         return ldpc_set_error(LDPC_EINVAL, "encode: d_info and d_codeword overlap");
     HIP_TRY(hipSetDevice(c->device));
     if (launch_dvbs2_encode(c->enc, d_info, d_codeword, batch, (hipStream_t)s))
+        return ldpc_set_error(LDPC_EDEVICE, "encode: %s", hipGetErrorString(hipGetLastError()));
+    return LDPC_OK;
+}
+
+// attach a general encoder (genc_host.cpp): uploads P and the position tables of a
+// code that needs them; an Annex-B code's encoder only marks the context, its
+// table went up with the context
+extern "C" int ldpc_ctx_set_encoder(ldpc_ctx *c, const ldpc_encoder *e)
+{
+    if (!c || !e) return ldpc_set_error(LDPC_EINVAL, "set_encoder: NULL %s", !c ? "context" : "encoder");
+    const ldpc_code *h = c->code;
+    if (e->code != h && (e->n != h->n || e->m != h->m || e->code_hash != genc_code_hash(h)))
+        return ldpc_set_error(LDPC_EINVAL, "set_encoder: the encoder was built for another code (%dx%d, the "
+                              "context's is %dx%d)", e->n, e->m, h->n, h->m);
+    if (c->device < 0) return host_only(c);
+    HIP_TRY(hipSetDevice(c->device));
+    // the previous encoder's tables may still be read by queued launches
+    if (c->genc.valid) HIP_TRY(hipDeviceSynchronize());
+    genc_free(&c->genc);
+    c->genc_attached = false;
+    c->genc_ira = e->ira;
+    if (!e->ira) {
+        int rc = genc_upload(e, &c->genc);
+        if (rc != LDPC_OK) return rc;
+    }
+    c->genc_attached = true;
+    return LDPC_OK;
+}
+
+// device twin of ldpc_encode (genc_host.cpp): no scratch, so any batch
+extern "C" int ldpc_encode_async(ldpc_ctx *c, void *s, const uint8_t *d_info, uint8_t *d_codeword, int batch)
+{
+    if (!c || batch < 0 || (batch > 0 && (!d_info || !d_codeword)))
+        return ldpc_set_error(LDPC_EINVAL, "encode args");
+    if (c->device < 0) return host_only(c);
+    if (!c->genc_attached)
+        return ldpc_set_error(LDPC_EINVAL, "encode: no encoder attached to the context (ldpc_ctx_set_encoder)");
+    if (c->genc_ira) return ldpc_dvbs2_encode_async(c, s, d_info, d_codeword, batch);   // the IRA kernel
+    if (batch == 0) return LDPC_OK;
+    const ldpc_code *h = c->code;
+    const uintptr_t i0 = (uintptr_t)d_info, c0 = (uintptr_t)d_codeword;
+    if (i0 < c0 + (size_t)batch * h->n && c0 < i0 + (size_t)batch * (h->n - h->m))
+        return ldpc_set_error(LDPC_EINVAL, "encode: d_info and d_codeword overlap");
+    HIP_TRY(hipSetDevice(c->device));
+    if (launch_genc(c->genc, d_info, d_codeword, batch, (hipStream_t)s))
         return ldpc_set_error(LDPC_EDEVICE, "encode: %s", hipGetErrorString(hipGetLastError()));
     return LDPC_OK;
 }

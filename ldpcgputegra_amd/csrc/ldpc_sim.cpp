@@ -10,12 +10,18 @@
 //
 //   ldpc_sim -code dvbs2_r1_2 -min 0.8 -max 1.2 -pas 0.1 -iter 50 -fer 100
 //            [-batch 4096] [-frames 1000000] [-OMS 1 | -NMS 29 | -MS]
-//            [-encoder [-fresh]] [-et] [-gpus N] [-seed S] [-kernel K]
+//            [-encoder [-fresh] | -gencoder [-fresh]] [-et] [-gpus N] [-seed S]
+//            [-kernel K]
 //
 // -encoder alone draws 64 codewords once on the host and replicates them over
 // every batch; -encoder -fresh draws new information bits and encodes them on
 // the GPU for every frame, as the reference's chain does per frame
-// (code/x86/main_p.cpp:431-445, 490-498).
+// (code/x86/main_p.cpp:431-445, 490-498).  -encoder is the DVB-S2 IRA encoder
+// (Annex-B codes only); -gencoder does the same through the general encoder
+// (ldpc_encoder_create / ldpc_encode / ldpc_encode_async), so it takes any
+// code.  Errors are counted over the first K codeword positions either way:
+// the information bits of a systematic code; for a code whose encoder is not
+// systematic (ldpc_encoder_info) they are K code bits, some of them parity.
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -38,7 +44,7 @@ struct Opt {
     double min = 0.5, max = 3.0, pas = 0.1;
     int iter = 30, fer = 100, batch = 4096, gpus = 1, kernel = 0;
     long frames = 1 << 20;
-    bool encoder = false, fresh = false;
+    bool encoder = false, gencoder = false, fresh = false;
     ldpc_params p{};
     uint64_t seed = 1;
 };
@@ -72,10 +78,11 @@ struct Totals {
 };
 
 void worker(int dev, const ldpc_code *h, const Opt &o, double sigma, Totals &tot, int n, int k,
-            const std::vector<uint8_t> &pool, int pool_n)
+            const std::vector<uint8_t> &pool, int pool_n, const ldpc_encoder *genc)
 {
     ldpc_ctx *ctx;
     CHECK(ldpc_ctx_create(h, dev, o.batch, &ctx));
+    if (genc && o.fresh) CHECK(ldpc_ctx_set_encoder(ctx, genc));
     if (o.kernel) CHECK(ldpc_ctx_set_kernel(ctx, o.kernel));
     void *stream;
     CHECK(ldpc_ctx_stream(ctx, &stream));
@@ -97,7 +104,7 @@ void worker(int dev, const ldpc_code *h, const Opt &o, double sigma, Totals &tot
             fprintf(stderr, "hipMalloc failed\n");
             exit(1);
         }
-    } else if (o.encoder) {
+    } else if (o.encoder || o.gencoder) {
         // the codeword pool replicated over the batch (noise differs per codeword)
         std::vector<uint8_t> rep((size_t)o.batch * n);
         for (int b = 0; b < o.batch; b++) memcpy(&rep[(size_t)b * n], &pool[(size_t)(b % pool_n) * n], n);
@@ -112,7 +119,8 @@ void worker(int dev, const ldpc_code *h, const Opt &o, double sigma, Totals &tot
         (void)hipMemsetAsync(d_cnt, 0, 16, (hipStream_t)stream);
         if (o.fresh) {
             CHECK(ldpc_info_bits_async(ctx, stream, d_info, o.batch, first, o.seed));
-            CHECK(ldpc_dvbs2_encode_async(ctx, stream, d_info, d_cw, o.batch));
+            if (genc) CHECK(ldpc_encode_async(ctx, stream, d_info, d_cw, o.batch));
+            else CHECK(ldpc_dvbs2_encode_async(ctx, stream, d_info, d_cw, o.batch));
         }
         CHECK(ldpc_awgn_i8_async(ctx, stream, d_llr, o.batch, first, o.seed, table, d_cw));
         CHECK(ldpc_decode_i8_async(ctx, stream, d_llr, d_hard, nullptr, nullptr, o.batch, o.iter, &o.p));
@@ -159,6 +167,7 @@ int main(int argc, char **argv)
         else if (a == "-NMS") { o.p.algo = LDPC_ALGO_NMS; o.p.factor = atoi(nxt()); }
         else if (a == "-MS") o.p.algo = LDPC_ALGO_MS;
         else if (a == "-encoder") o.encoder = true;
+        else if (a == "-gencoder") o.gencoder = true;
         else if (a == "-fresh") o.fresh = true;
         else if (a == "-et") o.p.early_term = 1;
         else {
@@ -166,7 +175,12 @@ int main(int argc, char **argv)
             return 2;
         }
     }
-    if (o.fresh && !o.encoder) {
+    if (o.encoder && o.gencoder) {
+        fprintf(stderr, "usage: -encoder (DVB-S2 IRA encoder) and -gencoder (general encoder, any code) exclude "
+                        "each other\n");
+        return 2;
+    }
+    if (o.fresh && !o.encoder && !o.gencoder) {
         fprintf(stderr, "usage: -fresh (new codewords every frame) needs -encoder\n");
         return 2;
     }
@@ -183,15 +197,19 @@ int main(int argc, char **argv)
     }
     std::vector<uint8_t> pool;
     int pool_n = 0;
+    ldpc_encoder *genc = nullptr;
+    if (o.gencoder) CHECK(ldpc_encoder_create(h, &genc));
     if (o.fresh) {
-        CHECK(ldpc_dvbs2_encode(h, nullptr, nullptr, 0));   // the library's verdict on the code, before any GPU work
-    } else if (o.encoder) {
+        // the library's verdict on the code, before any GPU work
+        if (!genc) CHECK(ldpc_dvbs2_encode(h, nullptr, nullptr, 0));
+    } else if (o.encoder || o.gencoder) {
         pool_n = 64;
         std::vector<uint8_t> info((size_t)pool_n * k);
         std::mt19937_64 rng(o.seed);
         for (auto &b : info) b = rng() & 1;
         pool.resize((size_t)pool_n * n);
-        CHECK(ldpc_dvbs2_encode(h, info.data(), pool.data(), pool_n));
+        if (genc) CHECK(ldpc_encode(genc, info.data(), pool.data(), pool_n));
+        else CHECK(ldpc_dvbs2_encode(h, info.data(), pool.data(), pool_n));
     }
     printf("(II) code %s N=%d K=%d E=%d | %s | iters %d | batch %d x %d GPU(s)\n", o.code.c_str(), n, k, e,
            o.p.algo == LDPC_ALGO_NMS ? "NMS" : (o.p.algo == LDPC_ALGO_MS ? "MS" : "OMS"), o.iter, o.batch, o.gpus);
@@ -201,7 +219,7 @@ int main(int argc, char **argv)
         auto t0 = std::chrono::steady_clock::now();
         std::vector<std::thread> th;
         for (int d = 0; d < o.gpus; d++)
-            th.emplace_back(worker, d, h, std::cref(o), sigma, std::ref(tot), n, k, std::cref(pool), pool_n);
+            th.emplace_back(worker, d, h, std::cref(o), sigma, std::ref(tot), n, k, std::cref(pool), pool_n, genc);
         for (auto &t : th) t.join();
         const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         const long fr = tot.frames, fe = tot.fe, be = tot.be;
@@ -216,6 +234,7 @@ int main(int argc, char **argv)
                eb, sigma, fr, fe, be, ber, fer, mbps);
         fflush(stdout);
     }
+    ldpc_encoder_destroy(genc);
     ldpc_code_destroy(h);
     return 0;
 }

@@ -219,6 +219,21 @@ class Decoder:
         self._on_stream(stream, lambda s: _lib.check(_lib.lib().ldpc_dvbs2_encode_async(
             self._ctx, s, self._ptr(info), self._ptr(codeword), B)), self.device)
 
+    def set_encoder(self, enc):
+        """Attach a general encoder (Code.encoder()) of this decoder's code:
+        uploads its matrix (synchronous).  encode_any_device needs it."""
+        _lib.check(_lib.lib().ldpc_ctx_set_encoder(self._ctx, enc.handle))
+        self._encoder = enc   # alive as long as it is attached
+
+    def encode_any_device(self, info, codeword, stream=None):
+        """General encoding on the device, any code: info uint8 [batch, K]
+        (taken & 1) -> codeword uint8 [batch, N], byte-equal to Encoder.encode."""
+        B = info.shape[0]
+        assert info.is_contiguous() and info.numel() == B * self.code.k_info
+        assert codeword.is_contiguous() and codeword.numel() == B * self.code.n
+        self._on_stream(stream, lambda s: _lib.check(_lib.lib().ldpc_encode_async(
+            self._ctx, s, self._ptr(info), self._ptr(codeword), B)), self.device)
+
     def quantize_device(self, y, q, factor=8, sat_neg=-31, sat_pos=31, stream=None):
         """float -> int8 LLR on the device (CFastFixConversion::generate's rule:
         clamp(trunc(factor * y), sat_neg, sat_pos)); y float32, q int8, same numel."""
