@@ -31,7 +31,11 @@
 //   empty check slot use a second sink V[N+1] no live check reads.
 // Min / max and the xor are order-independent and every per-edge op (sub,
 // add, the constant's sub / max or mul) is the oracle's, so the result is
-// bit-identical (the float tests keep a 1e-6 tolerance).
+// bit-identical to the oracle's decode of the LLRs with every zero +0.0 (the
+// load below), and equal to its decode of the LLRs as given except for the
+// sign of a zero; subnormals order as integers like any float and are kept.
+// tests/test_gpu_float_domain.py holds the kernel to exactly that, on tied,
+// zero, -0.0, subnormal and large LLRs.
 #include <algorithm>
 #include <cmath>
 #include <vector>

@@ -260,6 +260,13 @@ __global__ void __launch_bounds__(64) stairf_et_init_k(uint8_t *live, uint32_t *
     if (b < batch) iters_used[b] = iters;
 }
 
+// without early termination every codeword runs all the iterations
+__global__ void __launch_bounds__(64) stairf_fill_iters_k(int32_t *iters_used, int batch, int iters)
+{
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b < batch) iters_used[b] = iters;
+}
+
 __global__ void __launch_bounds__(64) stairf_syndrome_k(const float *V, const uint32_t *ev, const uint8_t *live,
                                                         uint32_t *bad, int m, int d0, int chunk, int stride)
 {
@@ -415,7 +422,14 @@ int launch_stairf(const DecodeLaunch &L, const StairfCode &sc, hipStream_t s)
         }
         return -1;
     };
-    if (!L.early) return L.iters <= 0 ? 0 : run();
+    if (!L.early) {
+        if (L.iters_used) {   // as the other kernels report it (generic.hip, coop3.hip fill_iters3_k)
+            hipLaunchKernelGGL(stairf_fill_iters_k, dim3((L.batch + 63) / 64), dim3(64), 0, s, L.iters_used, L.batch,
+                               L.iters);
+            if (hipGetLastError() != hipSuccess) return -1;
+        }
+        return L.iters <= 0 ? 0 : run();
+    }
     // early termination: one launch per iteration, then the syndrome
     const int cb = L.stride / 64;
     hipLaunchKernelGGL(stairf_et_init_k, dim3(cb), dim3(64), 0, s, L.live, L.bad, L.iters_used, L.batch, L.stride,
