@@ -203,6 +203,11 @@ int ldpc_ctx_last_skipped(ldpc_ctx *ctx, int *kernel);
  * 8192 codewords: the codewords still decoding compacted every
  * LDPC_COOP3_ET_STEP iterations), 0 when it ran as one launch. */
 int ldpc_ctx_last_et_stage(ldpc_ctx *ctx, int *first_stage_iters);
+/* Launch shape of the last decode on the LDS-resident kernel (7): lanes per
+ * codeword (64 / codewords per wave; it grows at small batches, which spread
+ * over more waves) and whether two lanes shared a check (split = 1); 0 / 0
+ * when the last decode ran another kernel.  (Introspection for tests.) */
+int ldpc_ctx_last_lds_shape(ldpc_ctx *ctx, int *lanes_per_codeword, int *split);
 /* Kernel timing (bench / profiling): when enabled, every decode records HIP
  * events around the decode kernel on the stream it is launched on;
  * ldpc_ctx_kernel_time returns the summed kernel time and launch count since

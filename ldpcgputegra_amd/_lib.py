@@ -88,6 +88,7 @@ SIGNATURES = {
     "ldpc_ctx_last_kernel": (I, [P, C.POINTER(I)]),
     "ldpc_ctx_last_skipped": (I, [P, C.POINTER(I)]),
     "ldpc_ctx_last_et_stage": (I, [P, C.POINTER(I)]),
+    "ldpc_ctx_last_lds_shape": (I, [P, C.POINTER(I), C.POINTER(I)]),
     "ldpc_ctx_profile": (I, [P, I]),
     "ldpc_ctx_kernel_time": (I, [P, C.POINTER(C.c_double), C.POINTER(I), I]),
     "ldpc_decode_i8": (I, [P, P, P, I, I, C.POINTER(ldpc_params)]),

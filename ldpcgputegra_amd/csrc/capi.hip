@@ -74,6 +74,8 @@ struct ldpc_ctx {
                                     // (4 and 6, windowed2 S32 and coop2, were superseded and removed)
     int last_kernel = 0;
     int last_et_stage = 0;          // coop3 staged early termination: first-stage iterations (0: one launch)
+    int last_lds_lanes = 0;         // kernel 7's last launch: lanes per codeword, two lanes per check or not
+    int last_lds_split = 0;         // (0 / 0 when the last decode was not kernel 7)
     int last_skipped = 0;   // the preferred kernel the last decode could not use at its batch size (0: none)
     int lds_pad = 0;        // extra dynamic LDS per windowed2 workgroup (ldpc_ctx_set_lds_pad)
     hipStream_t stream = nullptr;
@@ -329,6 +331,14 @@ extern "C" int ldpc_ctx_last_et_stage(ldpc_ctx *c, int *k)
     return LDPC_OK;
 }
 
+extern "C" int ldpc_ctx_last_lds_shape(ldpc_ctx *c, int *lanes_per_codeword, int *split)
+{
+    if (!c || !lanes_per_codeword || !split) return ldpc_set_error(LDPC_EINVAL, "NULL");
+    *lanes_per_codeword = c->last_lds_lanes;
+    *split = c->last_lds_split;
+    return LDPC_OK;
+}
+
 extern "C" int ldpc_ctx_get_kernel(ldpc_ctx *c, int *k)
 {
     if (!c || !k) return ldpc_set_error(LDPC_EINVAL, "NULL");
@@ -426,6 +436,7 @@ static int decode_device(ldpc_ctx *c, Scratch &sc, hipStream_t s, const void *d_
         return ldpc_set_error(LDPC_EUNSUPPORTED, "kernel %d selected but not applicable to these params", c->kernel);
     c->last_kernel = kern;
     if ((kern == 7 || kern == 9) && alloc_only) return LDPC_OK;
+    c->last_lds_lanes = c->last_lds_split = 0;
     if (kern == 7 && nm_ld) {   // node-major input: transpose it to frame-major scratch first
         if ((rc = ensure(&sc.d_msg, &sc.msg_bytes, (size_t)h->n * batch)) != LDPC_OK) return rc;
         if (launch_deinterleave_i8((const int8_t *)d_llr, nullptr, (int8_t *)sc.d_msg, h->n, batch, (int)nm_ld, s))
@@ -458,7 +469,8 @@ static int decode_device(ldpc_ctx *c, Scratch &sc, hipStream_t s, const void *d_
         }
         const int lr = kern == 9 ? launch_ldsep(c->lds, h, (const float *)d_llr, d_hard, (float *)d_soft, batch,
                                                 n_iter, L, s)
-                                 : launch_lds(c->lds, h, d_llr, d_hard, d_soft, batch, n_iter, L, s);
+                                 : launch_lds(c->lds, h, d_llr, d_hard, d_soft, batch, n_iter, L, s,
+                                              &c->last_lds_lanes, &c->last_lds_split);
         if (c->profile) {
             HIP_TRY(hipEventRecord(ev1, s));
             c->events.emplace_back(ev0, ev1);

@@ -30,6 +30,8 @@ int ldsep_upload(const ldpc_code *h, const std::vector<int4> &layers, LdsCode *l
 bool ldsep_applicable(const ldpc_code *h, const LdsCode &lc, bool is_float);
 int launch_ldsep(const LdsCode &lc, const ldpc_code *h, const float *llr, uint8_t *hard, float *soft, int batch,
                  int iters, const DecodeLaunch &L, hipStream_t s);
-// reads frame-major llr, writes frame-major hard / soft directly (no interleave)
+// reads frame-major llr, writes frame-major hard / soft directly (no interleave);
+// *lanes_per_codeword / *split (either may be null): the shape launched
 int launch_lds(const LdsCode &lc, const ldpc_code *h, const void *llr, uint8_t *hard, void *soft, int batch,
-               int iters, const DecodeLaunch &L, hipStream_t s);
+               int iters, const DecodeLaunch &L, hipStream_t s, int *lanes_per_codeword = nullptr,
+               int *split = nullptr);

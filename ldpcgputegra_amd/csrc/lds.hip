@@ -433,7 +433,7 @@ bool lds_preferred(const ldpc_code *h, const LdsCode &lc, bool is_float)
 }
 
 int launch_lds(const LdsCode &lc, const ldpc_code *h, const void *llr, uint8_t *hard, void *soft, int batch,
-               int iters, const DecodeLaunch &L, hipStream_t s)
+               int iters, const DecodeLaunch &L, hipStream_t s, int *lanes_per_codeword, int *split_out)
 {
     if (!lds_applicable(h, lc, L.is_float)) return -1;
     LdsArgs a{};
@@ -455,6 +455,8 @@ int launch_lds(const LdsCode &lc, const ldpc_code *h, const void *llr, uint8_t *
     while (lg < 6 && (batch << lg) / 64 < 2 * kLdsSimds) lg++;
     const bool split = (1 << lg) >= 2 * lc.max_width;
     a.lpc_log2 = lg;
+    if (lanes_per_codeword) *lanes_per_codeword = 1 << lg;
+    if (split_out) *split_out = split ? 1 : 0;
     a.algo = L.algo;
     a.param = L.param;
     a.var_min = L.var_min;

@@ -99,6 +99,14 @@ class Decoder:
         return k.value
 
     @property
+    def last_lds_shape(self):
+        """(lanes per codeword, two lanes per check) of the last decode's launch
+        of the LDS-resident kernel (7); (0, False) when it ran another kernel."""
+        lanes, split = C.c_int(), C.c_int()
+        _lib.check(_lib.lib().ldpc_ctx_last_lds_shape(self._ctx, C.byref(lanes), C.byref(split)))
+        return lanes.value, bool(split.value)
+
+    @property
     def last_skipped(self):
         """Name of the fastest kernel of this code that the last automatic
         selection could not use for its parameters (e.g. msg_max > 63 on the

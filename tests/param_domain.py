@@ -161,15 +161,16 @@ _oracle = {}
 _pool = None
 
 
-def oracle_decode(code, key, llr, params, iters, early=False):
+def oracle_decode(code, key, llr, params, iters, early=False, table=None):
     """(hard, soft, iters_used) of oracle.decode_i8 on llr (int8 [B, N]),
     read-only and cached per (code, input, params, iters, early); `key` names
-    the input.  The batch is split into slices of at most 16 codewords (fewer
-    where that keeps every thread busy) over oracle.host_threads() Python
-    threads (the ctypes call releases the GIL): oracle_decode_i8_mt_ex runs
-    for the default ranges only."""
+    the input.  `table`: the Table of a code that is no shipped one (`code`
+    then only names it in the cache).  The batch is split into slices of at
+    most 16 codewords (fewer where that keeps every thread busy) over
+    oracle.host_threads() Python threads (the ctypes call releases the GIL):
+    oracle_decode_i8_mt_ex runs for the default ranges only."""
     global _pool
-    t = load_table(code)
+    t = table if table is not None else load_table(code)
     ck = (code, key, params, iters, bool(early))
     if ck not in _oracle:
         if _pool is None:
