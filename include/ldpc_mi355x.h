@@ -256,7 +256,20 @@ void ldpc_host_free(void *ptr);
  * (the reference's decode_stream callers, code/gpu_fixed/test.cpp:347-393, and
  * torch's default stream); the context's own non-blocking stream
  * (ldpc_ctx_stream) is used only when passed explicitly.
- * soft (optional): final V per bit; iters_used (optional): per codeword. */
+ * soft (optional): final V per bit; iters_used (optional): per codeword.
+ *
+ * Buffer contract of every device-pointer entry point (decode, mixed decode,
+ * channel, quantiser, bit source, encoders, error count):
+ *  - a device buffer needs only the natural alignment of its element type:
+ *    1 byte for int8 / uint8, 4 for float / int32, 8 for the error counters.
+ *    A contiguous slice of a larger allocation is a valid argument; wider
+ *    alignment (16 bytes) only selects faster load / store paths, never
+ *    another result;
+ *  - outputs are [batch][N] (iters_used: [batch]): rows beyond `batch` and
+ *    bytes outside that range are never written, whatever group size the
+ *    kernel works in; batch 0 writes nothing;
+ *  - node-major input: columns batch .. ld-1 of a row are never read as data
+ *    (they may hold anything). */
 int ldpc_decode_i8_async(ldpc_ctx *ctx, void *hip_stream, const int8_t *d_llr, uint8_t *d_hard,
                          int8_t *d_soft, int32_t *d_iters_used, int batch, int n_iter,
                          const ldpc_params *p);
@@ -401,7 +414,10 @@ int ldpc_quantize_f32_i8_async(ldpc_ctx *ctx, void *hip_stream, const float *d_y
 int ldpc_quantize_f32_i8(ldpc_ctx *ctx, const float *y, int8_t *q, long count, int factor, int sat_neg,
                          int sat_pos);
 /* Count bit errors over the first k positions of each codeword vs d_ref
- * (NULL = all-zero); d_counts[0] += bit errors, d_counts[1] += frame errors. */
+ * (NULL = all-zero); d_counts[0] += bit errors, d_counts[1] += frame errors.
+ * A position is an error when bit 0 of d_hard and bit 0 of d_ref differ: the
+ * other bits of a d_ref byte are ignored, as the encoders take info & 1 (the
+ * same holds for the counting decodes below). */
 int ldpc_count_errors_async(ldpc_ctx *ctx, void *hip_stream, const uint8_t *d_hard, int batch,
                            int k, const uint8_t *d_ref, unsigned long long *d_counts);
 /* Decode and count in one call: ldpc_decode_*_async followed by

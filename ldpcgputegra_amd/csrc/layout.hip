@@ -213,12 +213,12 @@ __global__ void __launch_bounds__(64) count_errors_k(const uint8_t *__restrict__
         const int m = k / 16;
 #pragma unroll 4
         for (int i = threadIdx.x; i < m; i += 64) errs += e16(h16[i], r16 ? r16[i] : z);
-    } else if ((n & 3) == 0 && (k & 3) == 0) {
+    } else if ((n & 3) == 0 && (k & 3) == 0 && ((uintptr_t)hard & 3) == 0 && ((uintptr_t)ref & 3) == 0) {
         const uint32_t *h4 = (const uint32_t *)h, *r4 = (const uint32_t *)r;
         for (int i = threadIdx.x; i < k / 4; i += 64)
             errs += __builtin_popcount((h4[i] ^ (r4 ? r4[i] : 0u)) & 0x01010101u);
     } else {
-        for (int i = threadIdx.x; i < k; i += 64) errs += (h[i] != (r ? r[i] : 0));
+        for (int i = threadIdx.x; i < k; i += 64) errs += (h[i] ^ (r ? r[i] : 0)) & 1;   // bit 0, as the vector paths
     }
     for (int off = 32; off > 0; off >>= 1) errs += __shfl_xor(errs, off);
     if (threadIdx.x == 0 && errs) {

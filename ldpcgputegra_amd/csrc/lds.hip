@@ -260,7 +260,9 @@ __global__ void __launch_bounds__(64) lds_decode(LdsArgs a)
     }
     const T *src = (const T *)a.llr + (size_t)b * N;
     if (active) {
-        if ((N * sizeof(T)) % 16 == 0) {
+        // 16-B loads when every row starts 16-B aligned (wave-uniform: the caller's
+        // buffer needs only the alignment of T, include/ldpc_mi355x.h)
+        if ((N * sizeof(T)) % 16 == 0 && ((uintptr_t)a.llr & 15) == 0) {
             const uint4 *g = (const uint4 *)src;
             uint4 *l = (uint4 *)V;
 #pragma unroll 8

@@ -162,7 +162,7 @@ __global__ void __launch_bounds__(64 * EP_WAVES) ldsep_decode(EpArgs a)
         const uint8_t hb = v > 0.0f;   // code/x86/CTools/CTools.cpp:370
         if (hd) hd[i] = hb;
         if (sd) sd[i] = v;
-        if (a.cnt && i < a.cnt_k) errs += hb != (rf ? rf[i] : 0);   // CErrorAnalyzer.cpp:123-154
+        if (a.cnt && i < a.cnt_k) errs += (hb ^ (rf ? rf[i] : 0)) & 1;   // CErrorAnalyzer.cpp:123-154
     }
     if (a.cnt) {   // wave = codeword; then the workgroup's 4 codewords: one atomic pair per workgroup
         for (int o = 32; o > 0; o >>= 1) errs += __shfl_xor(errs, o);

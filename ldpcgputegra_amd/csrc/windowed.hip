@@ -58,6 +58,7 @@ struct WinArgs {
     int n_windows;
     int param, var_min, msg_max, early;
     int32_t *iters_used;
+    int batch;                 // codewords >= batch are padding: nothing of theirs is written to iters_used
 };
 
 LDPC_DEV int dpp_shr1(int old, int v)
@@ -287,13 +288,13 @@ __global__ void __launch_bounds__(64) windowed_decode(WinArgs a)
                 bad |= __shfl_xor(bad, 8, 64);
                 if (!bad) {
                     live = false;
-                    if (slot == 0 && a.iters_used) a.iters_used[b] = it;
+                    if (slot == 0 && a.iters_used && b < a.batch) a.iters_used[b] = it;
                 }
             }
             if (!__any(live)) break;
         }
     }
-    if (live && slot == 0 && a.iters_used) a.iters_used[b] = it;
+    if (live && slot == 0 && a.iters_used && b < a.batch) a.iters_used[b] = it;
 }
 
 template <int D0>
@@ -416,6 +417,7 @@ int launch_windowed(const DecodeLaunch &L, const WindowedCode &w, hipStream_t s)
     a.msg_max = L.msg_max;
     a.early = L.early;
     a.iters_used = L.iters_used;
+    a.batch = L.batch;
     const int grid = L.stride / G;   // stride is a multiple of 64 -> grid % 16 == 0
     switch (w.d0) {
     case 7: return launch_d<7>(a, L.algo, grid, s);

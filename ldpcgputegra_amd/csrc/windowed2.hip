@@ -53,6 +53,7 @@ struct W2Args {
     int g0_end, n_windows;
     int off, msg_max, early;
     int32_t *iters_used;
+    int batch;                 // codewords >= batch are padding: nothing of theirs is written to iters_used
 };
 
 // ---- lane shifts inside an S-lane row (S = 16: DPP row; S = 32: two rows)
@@ -427,13 +428,13 @@ __global__ void __launch_bounds__(64) windowed2_decode(W2Args a)
                 if (!bad) bad = syndrome_part<D0 - 1, S>(a, tab1, a.n_windows - a.g0_end, slot, row, b);
                 if (!bad) {
                     live = false;
-                    if (slot == 0 && a.iters_used) a.iters_used[b] = it;
+                    if (slot == 0 && a.iters_used && b < a.batch) a.iters_used[b] = it;
                 }
             }
             if (!__any(live)) break;
         }
     }
-    if (live && slot == 0 && a.iters_used) a.iters_used[b] = it;
+    if (live && slot == 0 && a.iters_used && b < a.batch) a.iters_used[b] = it;
 }
 
 }  // namespace
@@ -528,6 +529,7 @@ int launch_windowed2(const DecodeLaunch &L, const Windowed2Code &w, hipStream_t 
     a.msg_max = L.msg_max;
     a.early = L.early;
     a.iters_used = L.iters_used;
+    a.batch = L.batch;
     const int G = 64 / w.S;
     const int grid = L.stride / G;   // stride % 64 == 0 -> grid % 8 == 0
     if (w.S != 16) return -1;   // S = 32 (one codeword per 32 lanes) was superseded and removed

@@ -32,6 +32,11 @@ DVBS2 = ["dvbs2_r1_2", "dvbs2_r2_3", "dvbs2shape_r3_4", "dvbs2shape_r5_6", "dvbs
 # (r3/4 and r8/9, which have no early-termination case, sit between their neighbours)
 EBN0 = {"648x324": 2.0, "576x288": 2.0, "200x100": 2.0, "1944x972": 2.0, "dvbs2_r1_2": 2.0, "dvbs2_r2_3": 2.6,
         "dvbs2shape_r3_4": 3.0, "dvbs2shape_r5_6": 3.5, "dvbs2_r8_9": 4.2, "dvbs2_r9_10": 4.4}
+# the batch-edge tests (test_gpu_buffer_domain.py): 65 codewords of the fine grid, 16 iterations of min-sum.  r1/2
+# at its EBN0 stops every codeword (codewords 0 .. 16 after 7 .. 9 iterations, codeword 64 after 8); r8/9 at 3.7 dB
+# leaves 37 of the 65 running, codeword 64 among them (codewords 0 .. 16: 10 .. 16).  At 3.8 dB codeword 64 stops,
+# at 3.6 dB none of the first 17 does.
+EDGE_EBN0 = {"dvbs2_r1_2": 2.0, "dvbs2_r8_9": 3.7}
 STREAM = 10            # grid_input draws from streams `stream` and `stream + 1`
 
 _inputs = {}

@@ -91,17 +91,28 @@ ET_RECIPE = {"dvbs2_r1_2": (7.0, 12), "dvbs2_r2_3": (6.0, 12), "dvbs2shape_r3_4"
              "dvbs2shape_r5_6": (3.3, 12), "dvbs2_r8_9": (3.0, 12), "dvbs2_r9_10": (3.0, 12)}
 
 
-def et_input(code, batch):
-    """int8 [batch, N], read-only and cached: the saturated AWGN input of ET_RECIPE."""
-    key = ("et", code, batch)
+# The batch-edge recipe (test_buffer_domain_cpu.py, test_gpu_buffer_domain.py): 65 codewords, 16 iterations, the
+# default parameters (OMS 1, msg_max 31).  Wanted: stopped and still-running codewords among the first 17 (one
+# coop / coop3 group and a ragged one), and codeword 64 -- alone in its group at batch 65 -- stopping early for one
+# code and not for the other.  r1/2's ET_RECIPE input gives that already (iterations used by codewords 0 .. 16: 1, 2
+# and, for two of them, 16; codeword 64 stops after 1).  r8/9's stops every codeword at iteration 1 or 2, so its
+# margin goes down to 1.0 dB, where 8 of the 65 never stop, and the seed is the first of 41 .. 89 whose codeword 64
+# is one of those (65: codewords 0 .. 16 use 2 .. 4 iterations, codeword 2 all 16; 17.9 % of the bytes +-127).
+ET_EDGE = {"dvbs2_r1_2": (ET_SEED, 7.0, 12), "dvbs2_r8_9": (65, 1.0, 12)}
+
+
+def et_input(code, batch, recipe=None):
+    """int8 [batch, N], read-only and cached: the saturated AWGN input of
+    ET_RECIPE, or of `recipe` = (seed, margin, scale), e.g. ET_EDGE[code]."""
+    key = ("et", code, batch) if recipe is None else ("et", code, batch, tuple(recipe))
     if key not in _inputs:
         from test_gpu_coop3_r23 import EBN0
         from test_gpu_parity import ET_EBN0
         t = load_table(code)
-        margin, scale = ET_RECIPE[code]
+        seed, margin, scale = recipe if recipe is not None else (ET_SEED,) + tuple(ET_RECIPE[code])
         base = EBN0[code][0] if code in EBN0 else ET_EBN0[code]
         sigma = channel.sigma_from_ebn0(base + margin, t.k_info / t.n)
-        raw = channel.awgn_i8_host(t.n, batch, seed=ET_SEED, table=channel.i8_table(sigma))
+        raw = channel.awgn_i8_host(t.n, batch, seed=seed, table=channel.i8_table(sigma))
         x = np.clip(raw.astype(np.int32) * scale, -127, 127).astype(np.int8)
         x.setflags(write=False)
         _inputs[key] = x
