@@ -190,6 +190,12 @@ struct G3 {
 #define LDPC_C3_PRE_CHUNK_X 8    // pres of checks with >= this many info edges: stage-major chunks, two min chains
 #endif
 #ifndef LDPC_C3_POST_CHUNK_X
+#ifndef LDPC_C3_RD16
+#define LDPC_C3_RD16 1   // degree 7: the pre reads an info edge's V pair as the u16 the post writes (one address per edge)
+#endif
+#ifndef LDPC_C3_PACK2
+#define LDPC_C3_PACK2 1   // degree 7: the post packs two new V pairs per v_perm (stored by ds_write_b16 / _d16_hi)
+#endif
 #define LDPC_C3_POST_CHUNK_X 8   // posts of checks with >= this many info edges run new_v in stage-major chunks
 #endif
 template <int WS, int R, int SPW = 8>
@@ -313,7 +319,7 @@ struct Rec<D0, true> {
 template <int D0, bool KA = G3<D0>::KEEP_AD>
 struct PreIn {
     static constexpr int X = D0 - 2, XL = G3<D0>::XH, NW = G3<D0>::NW;
-    uint32_t v[XL + 1];               // raw V dwords (info edges from the line cache, the o edge from In)
+    uint32_t v[XL + 1];               // raw V (info edges from the line cache: dwords, or u16 pairs, Slab3::RD16; the o edge from In)
     uint32_t ad[KA ? XL : 1];         // the info pairs' byte offsets in the line cache
     uint32_t ma[NW], mb;              // old message record of this pair (MA0 .. MA(NW-1), MB; HALF: this half's)
     uint32_t meta, wx, wo;            // record words W_META, W_X, W_O
@@ -338,6 +344,17 @@ struct Slab3 {
     static constexpr int SX = G::HALF ? 14 : X;           // code slot of the x edge
     static constexpr int SO = G::HALF ? 15 : D0 - 1;      // code slot of the o edge
     static constexpr int SL = G::HALF ? 15 : X;           // the tail check's last edge
+    // degree 7: the pre reads an info edge's pair as a u16 at the address the
+    // post writes (kept in St3::ad) -- one address per edge instead of two, and
+    // a constant selector.  The two lanes sharing a dword still read the same
+    // bank in the same cycle (a broadcast), as the dword reads did.
+    static constexpr bool RD16 = LDPC_C3_RD16 && KA_ && D0 == 7;
+    static constexpr uint32_t USEL16 = 0x010d000du;       // unpack_v selector of a zero-extended u16 pair
+    // degree 7, fixed iterations: the post packs the new V of two edges with
+    // one v_perm (pack_v of the first in the low half, of the second in the
+    // high half) and stores the halves by ds_write_b16 / ds_write_b16_d16_hi:
+    // 3 v_perm for the 5 info edges and the x edge instead of 6
+    static constexpr bool PACK2 = LDPC_C3_PACK2 && D0 == 7;
     SM &sm;
     const Coop3Args &a;
     int k, kl, q, w, lane, tail;      // slot, slot in its 8-slot set, codeword pair, 8-slot set, lane
@@ -398,8 +415,13 @@ struct Slab3 {
 #pragma unroll
             for (int j = 0; j < XL; j++) in.ad[j] = rc.w(j) + lwr;
         }
+        if constexpr (RD16) {
 #pragma unroll
-        for (int j = 0; j < XL; j++) in.v[j] = *(const uint32_t *)(lcb() + rc.w(j) + lrd);   // the dword holding this lane's pair
+            for (int j = 0; j < XL; j++) in.v[j] = *(const unsigned short *)(lcb() + in.ad[j]);   // this lane's pair
+        } else {
+#pragma unroll
+            for (int j = 0; j < XL; j++) in.v[j] = *(const uint32_t *)(lcb() + rc.w(j) + lrd);   // the dword holding this lane's pair
+        }
         in.v[XL] = *(const uint32_t *)(inb + prd);
         if constexpr (G::HALF) {   // this half's (W0, W1) / (W2, W3) of the pair, and MB
             const uint2 mm = *(const uint2 *)(inb + mrd);
@@ -460,7 +482,7 @@ struct Slab3 {
         const uint32_t meta = in.meta;
         uint32_t v[XL + 1];
 #pragma unroll
-        for (int j = 0; j <= XL; j++) v[j] = unpack_v(in.v[j], usel);
+        for (int j = 0; j <= XL; j++) v[j] = unpack_v(in.v[j], RD16 && j < XL ? USEL16 : usel);
         if constexpr (KA) {
 #pragma unroll
             for (int j = 0; j < XL; j++) s.ad[j] = in.ad[j];
@@ -648,7 +670,8 @@ struct Slab3 {
         r0.z = perm(H, L, 0x05040100u);
         r1.z = perm(H, L, 0x07060302u);
         // (12-B ds_write_b96 stores of the three used dwords measured 1.7 %
-        // slower than these 16-B ones, r06c)
+        // slower than these 16-B ones, r06c; leaving the unused 4th dword
+        // undefined instead of 0 saves one v_mov and measured the same, r07)
         r0.w = r1.w = 0;
         uint4 *cp = (uint4 *)((char *)&sm.cst[cb][0][0][q] + (in.wo >> 16));
         if (!G::HALF || h == 0) {   // HALF: both lanes of a check hold the same constants
@@ -710,7 +733,21 @@ struct Slab3 {
                 else
                     put(ad, FZ ? perm(n, s.v[FZ_REREAD ? 0 : J], psel) : pack_v(n));   // FZ: pack_v of new / old per codeword
             };
-            if constexpr (XL < LDPC_C3_POST_CHUNK_X) {
+            uint32_t nlast = 0;   // PACK2: the last info edge's new V, packed with the x edge's below
+            if constexpr (PACK2 && !FZ && !LEAN && (XL & 1)) {
+                uint32_t n[XL];
+                static_for<0, XL>([&](auto jc) __attribute__((always_inline)) {
+                    constexpr int J = decltype(jc)::value;
+                    n[J] = nv(jc, s.c[J], s.a[J], min1, e1, e2);
+                });
+#pragma unroll
+                for (int j = 0; j + 1 < XL; j += 2) {
+                    const uint32_t w = perm(n[j + 1], n[j], 0x07050301u);   // pack_v(n[j]) | pack_v(n[j + 1]) << 16
+                    put(ad_of(g, s, j), w);
+                    put(ad_of(g, s, j + 1), w >> 16);
+                }
+                nlast = n[XL - 1];
+            } else if constexpr (XL < LDPC_C3_POST_CHUNK_X) {
                 static_for<0, XL>([&](auto jc) __attribute__((always_inline)) {
                     constexpr int J = decltype(jc)::value;
                     const uint32_t aJ = LEAN ? abs_sat(s.c[J], K.c510) : s.a[LEAN ? 0 : J];
@@ -756,7 +793,12 @@ struct Slab3 {
             if constexpr (MP >= 0) __builtin_amdgcn_s_setprio(MP);   // mid-phase wave priority (fast periods)
             // x edge: for converged codewords the chain passed V[p_{i-1}] unchanged
             const uint32_t nx = nv(std::integral_constant<int, SX>{}, cx, ax, min1, e1, e2);
-            if (lead) *sx = (unsigned short)(FZ ? perm(nx, xr, psel) : pack_v(nx));
+            if constexpr (PACK2 && !FZ && !LEAN && (XL & 1)) {
+                const uint32_t w = perm(nx, nlast, 0x07050301u);
+                put(ad_of(g, s, XL - 1), w);
+                *sx = (unsigned short)(w >> 16);
+            } else if (lead)
+                *sx = (unsigned short)(FZ ? perm(nx, xr, psel) : pack_v(nx));
             // the o edge: its code only (the next check rewrites V[o] as its x edge)
             const uint32_t aO = LEAN ? abs_r(s.c[XL], K.c510) : s.a[LEAN ? 0 : XL];
             msg_code<SO & 7>(s.c[XL], aO, min1, MA[SO >> 3]);
@@ -1546,7 +1588,8 @@ __global__ void __launch_bounds__(64 * (WS + 2)) coop3_decode(Coop3Args a)
     const int sk = GG::HALF ? 4 * sw + (lane >> 4) : 8 * sw + kl;   // this lane's slot
     const int sq = GG::HALF ? (lane >> 1) & 7 : q;                  // its codeword pair
     const int skl = sk & 7, sset = sk >> 3;                          // its set and slot in the set
-    Slab3<D0, WS, R, NMS, LEAN, KA> sl{sm,
+    using SL3 = Slab3<D0, WS, R, NMS, LEAN, KA>;
+    SL3 sl{sm,
                     a,
                     sk,
                     skl,
@@ -1687,11 +1730,15 @@ __global__ void __launch_bounds__(64 * (WS + 2)) coop3_decode(Coop3Args a)
                         t2 = stampL();
                     }
                     sl.template post<false, ET, MP1>(p - 1, xr, sp);
+                    // RD16: the priority drops before the pre's reads are issued, not after
+                    // them: no branch between a u16 read and its unpack (across one the
+                    // compiler zero-extends the value again, a v_and per edge)
+                    if (SL3::RD16 && fair) __builtin_amdgcn_s_setprio(P1);
                     sl.read_pre((s + 1) % NI, KA ? rcn : sl.read_rec(p + 1), in);
                 }
                 if constexpr (KA) rcn = sl.read_rec(p + 2);
                 if (STAMP) t1 = stampL();
-                if (fair) __builtin_amdgcn_s_setprio(P1);
+                if (!SL3::RD16 && fair) __builtin_amdgcn_s_setprio(P1);
                 sl.template pre<false, ET, MP2>(p + 1, in, sn);
                 if (STAMP) t3 = stampL();
             } else {

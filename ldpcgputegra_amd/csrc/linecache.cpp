@@ -491,7 +491,8 @@ int lc_build_plan(const std::vector<uint32_t> &tab, int recw, int nw, int S, int
         }
         return -1;
     };
-    // bank groups: a pre read (ds_read_b32) / post write (ds_write_b16) of info
+    // bank groups: a pre read (ds_read_b32; degree 7: a ds_read_u16 inside that
+    // dword, the same bank) / post write (ds_write_b16 / _d16_hi) of info
     // entry j serves slab wave w's slots 8w + 4h .. 8w + 4h + 3 in one 32-lane
     // half h; a piece's bank group is its position in its 128-B slot (slots are
     // 32 dwords = the 32 banks those instructions use), so 4 distinct pieces

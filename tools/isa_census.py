@@ -44,17 +44,48 @@ def regions(lines):
     yield start, len(lines), cur
 
 
-def coop3_census(funcs, kernel="coop3_decodeILi6ELi2ELb0ELb0ELb0E"):
+def coop3_slab_paths(L, mn):
+    """The unrolled steady periods of the slab waves (the barrier-delimited
+    regions holding all the fast-period variants: > 700 VALU), each split at
+    its branches.  The last four large blocks of a region are the post-first
+    path (waves 0-2: post + the pre's reads, then the pre) and the pre-first
+    path (waves 3-5: reads + pre, then the post); what precedes them is the
+    shared prefix and the guarded tail-window variant."""
+    out = []
+    start = 0
+    for i, m in enumerate(mn + ["s_barrier"]):
+        if m != "s_barrier":
+            continue
+        s, e, start = start, i, i + 1
+        if sum(1 for x in mn[s:e] if x.startswith("v_")) <= 700:
+            continue
+        marks = [s - 1] + [j for j in range(s, e) if mn[j].startswith(("s_cbranch", "s_branch"))] + [e]
+        blk = []
+        for x, y in zip(marks, marks[1:]):
+            c = collections.Counter(classify(m2) for m2 in mn[x + 1:y])
+            blk.append(dict(valu=c["valu"], lds=c["lds"], nop=c["nop"],
+                            waitcnt=sum(1 for m2 in mn[x + 1:y] if m2 == "s_waitcnt")))
+        big = [b for b in blk if b["valu"] >= 50]
+        if len(big) < 4:
+            continue
+        path = lambda bs: {k: sum(b[k] for b in bs) for k in ("valu", "lds", "nop", "waitcnt")}  # noqa: E731
+        out.append(dict(lines=[s, e], valu=sum(b["valu"] for b in blk), post_first=path(big[-4:-2]),
+                        pre_first=path(big[-2:])))
+    return out
+
+
+def coop3_census(funcs, kernel="coop3_decodeILi7ELi6ELi2ELb0ELb0ELb0E"):
     """One steady period of coop3 (DVB-S2 r1/2, WS = 6): the slab waves' fast
     period split at its branches (the shared prefix, the post variants for
     slab wave 0 / the others, the pre), a memory-wave period (between two
     period-closing vmcnt waits) and a chain block of 8 steps; VALU also as lane-ops per
     check x codeword (a slab lane = one check x 2 codewords; the memory and
-    chain waves serve a window's 48 checks x 16 codewords)."""
+    chain waves serve a window's 48 checks x 16 codewords); and the two slab
+    paths of each unrolled steady period (coop3_slab_paths)."""
     name = next(k for k in funcs if kernel in k)
     L = funcs[name]
     mn = [l.split()[0] if l.split() else "" for l in L]
-    out = {"kernel": name}
+    out = {"kernel": name, "slab_paths_per_unrolled_period": coop3_slab_paths(L, mn)}
     st = [i for i, l in enumerate(L) if mn[i] == "s_setprio" and l.split()[1] == "1"]
     s0 = st[len(st) // 2]
     b = s0
@@ -88,7 +119,7 @@ def coop3_census(funcs, kernel="coop3_decodeILi6ELi2ELb0ELb0ELb0E"):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("path")
-    ap.add_argument("kernel", nargs="?", default="coop3_decodeILi6ELi2ELb0ELb0ELb0E")
+    ap.add_argument("kernel", nargs="?", default="coop3_decodeILi7ELi6ELi2ELb0ELb0ELb0E")
     ap.add_argument("--min-valu", type=int, default=100)
     ap.add_argument("--hist", action="store_true")
     ap.add_argument("--coop3", action="store_true", help="coop3 steady-period census as JSON")
