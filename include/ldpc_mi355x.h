@@ -175,27 +175,37 @@ void ldpc_code_destroy(ldpc_code *h);
 int ldpc_ctx_create(const ldpc_code *h, int device, int max_batch, ldpc_ctx **out);
 void ldpc_ctx_destroy(ldpc_ctx *ctx);
 int ldpc_ctx_stream(ldpc_ctx *ctx, void **hip_stream);
-/* Select kernel family: 0 = auto, 1 = generic (per-edge messages),
- * 2 = windowed layered kernel (compressed messages), 3 = windowed2 (S = 16),
- * 5 = workgroup-cooperative DVB-S2 kernel (coop),
- * 7 = LDS-resident short-code kernel (whole state in LDS; int8 and float),
- * 8 = coop3 (DVB-S2 first-group degree 7: slab waves doing pre + post, i16 chain),
- * 9 = ldsep (float, short QC codes: one wave per codeword, one lane per edge;
- *     the automatic choice for float decodes of the codes it fits),
- * 11 = stairf (float, DVB-S2 staircase codes: S consecutive checks of 64/S
- *     codewords per wave, the staircase chain by DPP; the automatic choice for
- *     float decodes of those codes, early termination by one launch per
- *     iteration + a syndrome pass).
- * 4 and 6 (windowed2 S = 32, coop2) were superseded and are rejected
+/* Kernel families (ldpc_ctx_set_kernel / get_kernel / last_kernel /
+ * last_skipped; the functions take and return plain int).  4 and 6 (windowed2
+ * S = 32, coop2) were superseded: the values stay reserved and are rejected
  * with LDPC_EUNSUPPORTED. */
+typedef enum ldpc_kernel {
+    LDPC_KERNEL_AUTO = 0,       /* set_kernel: automatic choice; last_kernel: no decode yet */
+    LDPC_KERNEL_GENERIC = 1,    /* per-edge messages, any code */
+    LDPC_KERNEL_WINDOWED = 2,   /* windowed layered kernel (compressed messages) */
+    LDPC_KERNEL_WINDOWED2 = 3,  /* windowed2 (S = 16) */
+    LDPC_KERNEL_COOP = 5,       /* workgroup-cooperative DVB-S2 kernel */
+    LDPC_KERNEL_LDS = 7,        /* LDS-resident short-code kernel (whole state in LDS; int8 and float) */
+    LDPC_KERNEL_COOP3 = 8,      /* DVB-S2 first-group degree 7: slab waves doing pre + post, i16 chain */
+    LDPC_KERNEL_LDSEP = 9,      /* float, short QC codes: one wave per codeword, one lane per edge;
+                                   the automatic choice for float decodes of the codes it fits */
+    LDPC_KERNEL_HOST = 10,      /* last_kernel of a device -1 context (the host decoder); not selectable */
+    LDPC_KERNEL_STAIRF = 11     /* float, DVB-S2 staircase codes: S consecutive checks of 64/S codewords
+                                   per wave, the staircase chain by DPP; the automatic choice for float
+                                   decodes of those codes, early termination by one launch per
+                                   iteration + a syndrome pass */
+} ldpc_kernel;
+/* Select the kernel family (an ldpc_kernel value): LDPC_KERNEL_AUTO .. LDPC_KERNEL_LDSEP
+ * or LDPC_KERNEL_STAIRF.  A value outside 0 .. 11, or LDPC_KERNEL_HOST, is
+ * LDPC_EINVAL; a family that cannot schedule the context's code (the reserved
+ * 4 and 6 included) is LDPC_EUNSUPPORTED and leaves the selection as it was. */
 int ldpc_ctx_set_kernel(ldpc_ctx *ctx, int kernel);
 int ldpc_ctx_get_kernel(ldpc_ctx *ctx, int *kernel);
-/* Kernel family the last decode actually ran (1 generic, 2 windowed,
- * 3 windowed2 S=16, 5 coop, 7 lds, 8 coop3, 9 ldsep, 10 the host decoder of a
- * device -1 context, 11 stairf; 0 before the first decode). */
+/* Kernel family the last decode actually ran (an ldpc_kernel value;
+ * LDPC_KERNEL_HOST on a device -1 context, 0 before the first decode). */
 int ldpc_ctx_last_kernel(ldpc_ctx *ctx, int *kernel);
 /* The fastest kernel of this code that the last automatic selection could
- * not use for the call's parameters (8: coop3, 5: coop -- they take OMS / MS
+ * not use for the call's parameters (LDPC_KERNEL_COOP3, LDPC_KERNEL_COOP -- they take OMS / MS
  * with msg_max <= 63 and var range +-127), 0 when none was skipped. */
 int ldpc_ctx_last_skipped(ldpc_ctx *ctx, int *kernel);
 /* Early termination of the last decode on coop3 (kernel 8): the iterations of

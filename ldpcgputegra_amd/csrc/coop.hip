@@ -696,40 +696,6 @@ __global__ void fill_iters_k(int batch, int32_t *iters_used, int iters)
     if (b < batch) iters_used[b] = iters;
 }
 
-// codewords converging after this iteration (live, no failing check): copy
-// their V column; block = 64 codewords x a chunk of rows
-constexpr int kSnapRows = 128;
-// rows [r0, r1) of column b, 16 loads in flight per round (a lone thread's
-// strided column copy is latency-bound otherwise)
-__device__ __forceinline__ void copy_column(const int8_t *src, int8_t *dst, int stride, int b, int r0, int r1)
-{
-    int r = r0;
-    for (; r + 16 <= r1; r += 16) {
-        int8_t x[16];
-#pragma unroll
-        for (int i = 0; i < 16; i++) x[i] = src[(size_t)(r + i) * stride + b];
-#pragma unroll
-        for (int i = 0; i < 16; i++) dst[(size_t)(r + i) * stride + b] = x[i];
-    }
-    for (; r < r1; r++) dst[(size_t)r * stride + b] = src[(size_t)r * stride + b];
-}
-__global__ void __launch_bounds__(64) snapshot_k(const int8_t *V, int8_t *Vs, int stride, int batch, int rows,
-                                                 const uint8_t *live, const uint32_t *bad)
-{
-    const int b = blockIdx.x * 64 + threadIdx.x;
-    if (b >= batch || !live[b] || bad[b]) return;
-    copy_column(V, Vs, stride, b, blockIdx.y * kSnapRows, min(rows, (int)(blockIdx.y + 1) * kSnapRows));
-}
-
-// after the last iteration: converged codewords take their snapshot back
-__global__ void __launch_bounds__(64) merge_snapshot_k(int8_t *V, const int8_t *Vs, int stride, int batch, int rows,
-                                                       const uint8_t *live)
-{
-    const int b = blockIdx.x * 64 + threadIdx.x;
-    if (b >= batch || live[b]) return;
-    copy_column(Vs, V, stride, b, blockIdx.y * kSnapRows, min(rows, (int)(blockIdx.y + 1) * kSnapRows));
-}
-
 // live[] covers the padded stride: padding columns are never live, so a
 // workgroup's skip test (any live codeword) does not read stale bytes
 __global__ void early_init_k(int batch, int stride, uint8_t *live, uint32_t *bad, int32_t *iters_used, int iters)
@@ -1048,23 +1014,11 @@ int coop_early_after_iter(const DecodeLaunch &L, int it, hipStream_t s)
         const int v = (e && *e) ? atoi(e) : 64;
         return v >= 4 && v <= 4096 ? v : 64;
     }();
-    // V (and its snapshot Vs) rows are L.vpitch codewords apart (the padded
-    // pitch of the coop kernels); live / bad / iters_used are per codeword
+    // V rows are L.vpitch codewords apart (the padded pitch of the coop
+    // kernel); live / bad / iters_used are per codeword
     const dim3 sgrid((L.batch + 63) / 64, (L.m + kChunk - 1) / kChunk);
     hipLaunchKernelGGL(syndrome_k, sgrid, dim3(64), 0, s, (const int8_t *)L.V, L.vpitch, L.batch, L.d_edge_var,
                        L.d_group_deg, L.d_group_cnt, L.n_groups, L.m, kChunk, (const uint8_t *)L.live, L.bad);
-    if (L.Vs)
-        hipLaunchKernelGGL(snapshot_k, dim3((L.batch + 63) / 64, (L.n + kSnapRows - 1) / kSnapRows), dim3(64), 0, s,
-                           (const int8_t *)L.V, L.Vs, L.vpitch, L.batch, L.n, (const uint8_t *)L.live,
-                           (const uint32_t *)L.bad);
     hipLaunchKernelGGL(syndrome_finish_k, dim3(nb), dim3(256), 0, s, L.batch, L.live, L.bad, L.iters_used, it + 1);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-int coop_early_end(const DecodeLaunch &L, hipStream_t s)
-{
-    if (!L.Vs) return 0;
-    hipLaunchKernelGGL(merge_snapshot_k, dim3((L.batch + 63) / 64, (L.n + kSnapRows - 1) / kSnapRows), dim3(64), 0, s,
-                       (int8_t *)L.V, (const int8_t *)L.Vs, L.vpitch, L.batch, L.n, (const uint8_t *)L.live);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

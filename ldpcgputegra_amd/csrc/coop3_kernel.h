@@ -1,10 +1,11 @@
 // coop3_kernel.h -- the DVB-S2 staircase-code decoder, third generation: the
 // BASELINE.json headline path (DVB-S2 r1/2, 50 iterations, int8 OMS).
 // Bit-exact with the reference's CDecoder_OMS_fixed_SSE::decode_8bits
-// (code/x86/CDecoder/OMS/CDecoder_OMS_fixed_SSE.cpp:172-546), like coop.hip /
-// coop2.hip, whose window plan (coop_build_plan), message format and
-// packed-pair arithmetic (pk16.h) it shares.  What changes is the workgroup's
-// organisation, built from what bounds coop2 on MI355X:
+// (code/x86/CDecoder/OMS/CDecoder_OMS_fixed_SSE.cpp:172-546), like coop.hip,
+// whose window plan (coop_build_plan) it shares.  Message format and
+// packed-pair arithmetic (pk16.h) come from its predecessor coop2 (removed);
+// the workgroup's organisation is built from what bounded coop2 on MI355X
+// (DESIGN.md §8):
 //
 // * slab waves do BOTH halves of a check (pre: gather V + old messages,
 //   contributions, min1 / min2 / signs and the chain constants; post: new

@@ -1,5 +1,5 @@
-// kernels.h -- launch descriptors shared between the C-ABI (capi.hip) and the
-// kernel translation units.
+// kernels.h -- launch descriptors shared between the decode dispatcher
+// (dispatch.hip), the C-ABI (capi.hip) and the kernel translation units.
 #pragma once
 #include "kernels_common.h"
 
@@ -8,7 +8,7 @@ struct DecodeLaunch {
     void *V;
     void *msg;
     int stride;          // codeword slots (multiple of 64): the batch padded
-    int vpitch;          // V row pitch in codewords (>= stride; coop3 may pad it)
+    int vpitch;          // V row pitch in codewords (>= stride; coop pads it)
     int batch;
     int iters;
     int is_float;
@@ -24,10 +24,6 @@ struct DecodeLaunch {
     // early-termination scratch of the coop kernel ([stride] each)
     uint8_t *live;
     uint32_t *bad;
-    // coop2 early termination: V snapshot taken when a codeword converges
-    // (coop2 keeps iterating converged codewords that share a workgroup with
-    // live ones; the snapshot is merged back before the hard decisions)
-    int8_t *Vs;
     // coop3: V in the grouped layout Vg[stride / 16][rows][16 codewords],
     // vgroup bytes between groups (0: the row layout V[N][vpitch])
     size_t vgroup;

@@ -42,7 +42,7 @@ namespace {
 struct Opt {
     std::string code = "dvbs2_r1_2";
     double min = 0.5, max = 3.0, pas = 0.1;
-    int iter = 30, fer = 100, batch = 4096, gpus = 1, kernel = 0;
+    int iter = 30, fer = 100, batch = 4096, gpus = 1, kernel = LDPC_KERNEL_AUTO;
     long frames = 1 << 20;
     bool encoder = false, gencoder = false, fresh = false;
     ldpc_params p{};

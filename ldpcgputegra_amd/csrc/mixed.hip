@@ -118,7 +118,7 @@ extern "C" int ldpc_mixed_create(const ldpc_code *const *codes, int n_codes, int
     std::vector<bool> c3(nc, false);
     bool any_c3 = false;
     for (int c = 0; c < n_codes; c++) {
-        c3[c] = ldpc_ctx_has_kernel(mx->ctx[c], 8);
+        c3[c] = ldpc_ctx_has_kernel(mx->ctx[c], LDPC_KERNEL_COOP3);
         any_c3 = any_c3 || c3[c];
     }
     const char *pp = getenv("LDPC_MIXED_LDS_PAD");

@@ -1,5 +1,5 @@
-// pk16.h -- packed 16-bit helpers shared by the packed-pair DVB-S2 kernels
-// (coop2.hip, coop3.hip): two codewords per lane, one per 16-bit half.
+// pk16.h -- packed 16-bit helpers of the packed-pair DVB-S2 kernel
+// (coop3.hip): two codewords per lane, one per 16-bit half.
 //
 // An int8 value x sits in a half as R(x) = 256 x + 255 (value in the high
 // byte, low byte all ones) and a message m as C(m) = 256 m.  Then
