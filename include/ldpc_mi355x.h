@@ -410,6 +410,25 @@ int ldpc_awgn_i8_host(int n, int batch, uint64_t first_cw, uint64_t seed, const 
 int ldpc_awgn_i8_async(ldpc_ctx *ctx, void *hip_stream, int8_t *d_llr, int batch,
                        uint64_t first_cw, uint64_t seed, const uint32_t *table,
                        const uint8_t *d_codeword);
+/* The float channel, replacing CChanelAWGN_MKL::generate
+ * (code/x86/CChanel/CChanelAWGN_MKL.cpp:127-143): the unquantised form of the
+ * noise the int8 channel draws.  For element i of codeword first_cw + b:
+ *   u = splitmix64(((first_cw + b) * N + i) ^ (seed * 0xD1B54A32D192ED03)) >> 32
+ *   z = Phi^-1((u + 0.5) * 2^-32)            (double; |z| <= 6.34: 32 bits of u
+ *                                             cut off 2^-32 of the mass)
+ *   y = (float)(norm * (-amp + sigma * z)),  negated where the codeword bit is 1
+ * with sigma, amp and norm as in ldpc_awgn_i8_table_ex (all > 0).  Host and
+ * device give the same bits.  u is the int8 channel's for the same (seed,
+ * first_cw), so ldpc_quantize_f32_i8(y, factor, -sat, sat) reproduces
+ * ldpc_awgn_i8_* except at the edges of a quantisation cell (about 2e-6 of
+ * the samples), and float and int8 decoders can be compared on paired noise.
+ * y is [batch][N] floats, 4-byte aligned; codeword bits (0/1, [batch][N]) or
+ * NULL for the all-zero codeword.  LDPC_EINVAL for a NULL y, a negative batch
+ * or a non-positive sigma, amp or norm; batch 0 writes nothing. */
+int ldpc_awgn_f32_host(int n, int batch, uint64_t first_cw, uint64_t seed, double sigma, double amp, double norm,
+                       const uint8_t *codeword, float *y);
+int ldpc_awgn_f32_async(ldpc_ctx *ctx, void *hip_stream, float *d_y, int batch, uint64_t first_cw, uint64_t seed,
+                        double sigma, double amp, double norm, const uint8_t *d_codeword);
 /* float -> int8 LLR conversion, replacing CFastFixConversion::generate
  * (code/x86/CFixPointConversion/CFastFixConversion.cpp:55-65) and the GPU
  * converter (code/gpu_fixed/decoder_template/GPU_Scheduled_functions.cu:54-62):

@@ -120,6 +120,8 @@ SIGNATURES = {
     "ldpc_awgn_i8_table_ex": (I, [C.c_double, C.c_double, C.c_double, I, I, P]),
     "ldpc_awgn_i8_host": (I, [I, I, U64, U64, P, P, P]),
     "ldpc_awgn_i8_async": (I, [P, P, P, I, U64, U64, P, P]),
+    "ldpc_awgn_f32_host": (I, [I, I, U64, U64, C.c_double, C.c_double, C.c_double, P, P]),
+    "ldpc_awgn_f32_async": (I, [P, P, P, I, U64, U64, C.c_double, C.c_double, C.c_double, P]),
     "ldpc_count_errors_async": (I, [P, P, P, I, I, P, P]),
     "ldpc_decode_i8_count_async": (I, [P, P, P, P, P, P, I, I, C.POINTER(ldpc_params), I, P, P]),
     "ldpc_decode_f32_count_async": (I, [P, P, P, P, P, P, I, I, C.POINTER(ldpc_params), I, P, P]),

@@ -66,3 +66,24 @@ def awgn_i8_host(n, batch, seed, table, first_cw=0, codeword=None):
     t = np.ascontiguousarray(table, dtype=np.uint32)
     _lib.check(_lib.lib().ldpc_awgn_i8_host(n, batch, first_cw, seed, t.ctypes.data, cw, out.ctypes.data))
     return out
+
+
+def awgn_f32_host(n, batch, seed, sigma, amp=BPSK, normalize=False, first_cw=0, codeword=None):
+    """The float channel (``ldpc_awgn_f32_host``, bit-equal to
+    ``Decoder.awgn_f32_device``), in place of CChanelAWGN_MKL::generate:
+
+        u = the int8 generator's u,  z = Phi^-1((u + 0.5) * 2^-32)   (|z| <= 6.34)
+        y = float32(norm * (-amp + sigma z)),  negated where the codeword bit is 1
+
+    norm = 2 / sigma^2 with ``normalize``, else 1.  Quantising factor * y gives
+    ``awgn_i8_host`` of the same (seed, first_cw) except at the edges of a
+    quantisation cell."""
+    out = np.empty((batch, n), dtype=np.float32)
+    cw = None
+    if codeword is not None:
+        codeword = np.ascontiguousarray(codeword, dtype=np.uint8)
+        cw = codeword.ctypes.data
+    norm = 2.0 / (sigma * sigma) if normalize else 1.0
+    _lib.check(_lib.lib().ldpc_awgn_f32_host(n, batch, first_cw, seed, float(sigma), float(amp), float(norm), cw,
+                                             out.ctypes.data))
+    return out

@@ -528,6 +528,22 @@ extern "C" int ldpc_awgn_i8_async(ldpc_ctx *c, void *s, int8_t *d_llr, int batch
     return LDPC_OK;
 }
 
+// the float channel (generator: awgn_f32.h; host twin: ldpc_awgn_f32_host), where the reference calls
+// CChanelAWGN_MKL::generate (code/x86/CChanel/CChanelAWGN_MKL.cpp:127-143)
+extern "C" int ldpc_awgn_f32_async(ldpc_ctx *c, void *s, float *d_y, int batch, uint64_t first_cw, uint64_t seed,
+                                   double sigma, double amp, double norm, const uint8_t *d_codeword)
+{
+    if (!c || !d_y || batch < 0 || !(sigma > 0.0) || !(amp > 0.0) || !(norm > 0.0) || ((uintptr_t)d_y & 3))
+        return ldpc_set_error(LDPC_EINVAL, "awgn f32 args: y non-NULL and 4-byte aligned, batch>=0, sigma>0, "
+                                           "amp>0, norm>0");
+    if (c->device < 0) return host_only(c);
+    if (batch == 0) return LDPC_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    if (launch_awgn_f32(d_y, c->code->n, batch, first_cw, seed, sigma, amp, norm, d_codeword, (hipStream_t)s))
+        return ldpc_set_error(LDPC_EDEVICE, "awgn f32: %s", hipGetErrorString(hipGetLastError()));
+    return LDPC_OK;
+}
+
 // the bit source of the chain (the reference's CBitGenerator::generate): K = n - m bits per codeword
 extern "C" int ldpc_info_bits_async(ldpc_ctx *c, void *s, uint8_t *d_info, int batch, uint64_t first_cw,
                                     uint64_t seed)

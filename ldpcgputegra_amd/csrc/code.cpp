@@ -11,6 +11,7 @@
 
 #include "ldpc_internal.h"
 #include "coop.h"
+#include "awgn_f32.h"
 
 bool windowed_supported(const ldpc_code *h);   // windowed.hip
 int ldpc_plan_build(ldpc_code *h);             // plan.cpp
@@ -447,6 +448,24 @@ extern "C" int ldpc_awgn_i8_host(int n, int batch, uint64_t first_cw, uint64_t s
             int q = cnt - sat;
             if (codeword && codeword[(size_t)b * n + i]) q = -q;
             llr[(size_t)b * n + i] = (int8_t)q;
+        }
+    return LDPC_OK;
+}
+
+// The float channel's host twin (generator: awgn_f32.h; device: awgn_f32_k), where the reference calls
+// CChanelAWGN_MKL::generate (code/x86/CChanel/CChanelAWGN_MKL.cpp:127-143).  sigma, amp, norm as in
+// ldpc_awgn_i8_table_ex; the u of every element is the int8 channel's.
+extern "C" int ldpc_awgn_f32_host(int n, int batch, uint64_t first_cw, uint64_t seed, double sigma, double amp,
+                                  double norm, const uint8_t *codeword, float *y)
+{
+    if (n <= 0 || batch < 0 || !y || !(sigma > 0.0) || !(amp > 0.0) || !(norm > 0.0))
+        return ldpc_set_error(LDPC_EINVAL, "awgn f32 host args: n>0, batch>=0, y non-NULL, sigma>0, amp>0, norm>0");
+    const uint64_t key = seed * AWGN_KEY_MUL;
+    for (int b = 0; b < batch; b++)
+        for (int i = 0; i < n; i++) {
+            const size_t e = (size_t)b * n + i;
+            const float v = awgn_f32_sample((first_cw + b) * (uint64_t)n + i, key, sigma, amp, norm);
+            y[e] = (codeword && codeword[e]) ? -v : v;
         }
     return LDPC_OK;
 }

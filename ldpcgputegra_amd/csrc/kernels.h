@@ -72,5 +72,8 @@ int launch_scatter_rows(const void *src, void *dst, const int32_t *idx, int rows
 
 int launch_awgn_i8(int8_t *llr, int n, int batch, uint64_t first_cw, uint64_t seed, const AwgnTable &t,
                    const uint8_t *codeword, hipStream_t s);
+// float channel (awgn_f32.h): y[batch][n], 4-byte aligned
+int launch_awgn_f32(float *y, int n, int batch, uint64_t first_cw, uint64_t seed, double sigma, double amp,
+                    double norm, const uint8_t *codeword, hipStream_t s);
 int launch_count_errors(const uint8_t *hard, int n, int batch, int k, const uint8_t *ref,
                         unsigned long long *counts, hipStream_t s);

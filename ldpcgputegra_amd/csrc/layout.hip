@@ -12,6 +12,7 @@
 #include <climits>
 #include <algorithm>
 #include "kernels.h"
+#include "awgn_f32.h"
 
 namespace {
 
@@ -192,6 +193,39 @@ __global__ void __launch_bounds__(256) awgn_i8_k(int8_t *__restrict__ llr, int n
     }
 }
 
+// The float channel (awgn_f32.h has the generator).  idx = (first_cw + b) * n + i
+// is first_cw * n + e for the flat element e = b * n + i, so nothing is divided:
+// a lane hashes base + e.  Each lane owns 4 consecutive elements,
+// e = 4 * lane - shift .. + 3, where shift = the floats by which y is past a
+// 16-B boundary: &y[4 * lane - shift] is then 16-B aligned and the 4 samples
+// leave as one float4.  A lane whose 4 elements are not all inside [0, total)
+// (the first when shift > 0, the last) stores the inside ones one by one.
+// Alignment moves the lane boundaries, never a value.
+__global__ void __launch_bounds__(256) awgn_f32_k(float *__restrict__ y, long long total, int shift, uint64_t base,
+                                                  uint64_t key, double sigma, double amp, double norm,
+                                                  const uint8_t *__restrict__ cw)
+{
+    const long long lanes = (total + shift + 3) / 4;
+    for (long long g = (long long)blockIdx.x * 256 + threadIdx.x; g < lanes; g += (long long)gridDim.x * 256) {
+        const long long e0 = 4 * g - shift;
+        float v[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const long long e = e0 + j;
+            const bool in = e >= 0 && e < total;
+            const float s = awgn_f32_sample(base + (uint64_t)e, key, sigma, amp, norm);
+            v[j] = (in && cw && cw[e]) ? -s : s;
+        }
+        if (e0 >= 0 && e0 + 3 < total) {
+            *(float4 *)(y + e0) = make_float4(v[0], v[1], v[2], v[3]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+                if (e0 + j >= 0 && e0 + j < total) y[e0 + j] = v[j];
+        }
+    }
+}
+
 // one wave per codeword: hard decisions are 0/1 bytes, so the errors of a
 // dword are popcount((h ^ r) & 0x01010101); dword loads when the row allows
 __global__ void __launch_bounds__(64) count_errors_k(const uint8_t *__restrict__ hard, int n, int k,
@@ -346,6 +380,18 @@ int launch_awgn_i8(int8_t *llr, int n, int batch, uint64_t first_cw, uint64_t se
     int blocks = (int)std::min<size_t>((total + 255) / 256, 8192);
     if (blocks < 1) blocks = 1;
     hipLaunchKernelGGL(awgn_i8_k, dim3(blocks), dim3(256), 0, s, llr, n, batch, first_cw, seed, t, codeword);
+    return ok();
+}
+int launch_awgn_f32(float *y, int n, int batch, uint64_t first_cw, uint64_t seed, double sigma, double amp,
+                    double norm, const uint8_t *codeword, hipStream_t s)
+{
+    const long long total = (long long)n * batch;
+    if (total <= 0) return 0;
+    const int shift = (int)(((uintptr_t)y >> 2) & 3);
+    const long long lanes = (total + shift + 3) / 4;
+    const int blocks = (int)std::min<long long>((lanes + 255) / 256, 256 * 32);
+    hipLaunchKernelGGL(awgn_f32_k, dim3(blocks), dim3(256), 0, s, y, total, shift, first_cw * (uint64_t)n,
+                       seed * AWGN_KEY_MUL, sigma, amp, norm, codeword);
     return ok();
 }
 int launch_gather_rows(const void *src, void *dst, const int32_t *idx, int rows, int row_bytes, hipStream_t s)

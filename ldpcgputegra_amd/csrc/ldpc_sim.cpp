@@ -11,7 +11,17 @@
 //   ldpc_sim -code dvbs2_r1_2 -min 0.8 -max 1.2 -pas 0.1 -iter 50 -fer 100
 //            [-batch 4096] [-frames 1000000] [-OMS 1 | -NMS 29 | -MS]
 //            [-encoder [-fresh] | -gencoder [-fresh]] [-et] [-gpus N] [-seed S]
-//            [-kernel K]
+//            [-kernel K] [-f32 [-beta B] | -f32q]
+//
+// Three chains see the same noise (one u per element, the same first_cw and
+// seed scheme): the default draws the quantised int8 LLRs directly
+// (ldpc_awgn_i8_async -> int8 decode); -f32 draws float samples
+// (ldpc_awgn_f32_async, in place of CChanelAWGN_MKL::generate) and runs the
+// float decoders with the fused error count (ldpc_decode_f32_count_async;
+// -beta B is the float OMS offset or NMS factor, -OMS / -NMS / -MS choose the
+// algorithm, their int8 value is not used); -f32q is the reference's chain
+// stage by stage: float channel -> ldpc_quantize_f32_i8_async (8, +-31) -> the
+// int8 decode.  The JSON line names the chain ("i8", "f32", "f32q").
 //
 // -encoder alone draws 64 codewords once on the host and replicates them over
 // every batch; -encoder -fresh draws new information bits and encodes them on
@@ -44,7 +54,7 @@ struct Opt {
     double min = 0.5, max = 3.0, pas = 0.1;
     int iter = 30, fer = 100, batch = 4096, gpus = 1, kernel = LDPC_KERNEL_AUTO;
     long frames = 1 << 20;
-    bool encoder = false, gencoder = false, fresh = false;
+    bool encoder = false, gencoder = false, fresh = false, f32 = false, f32q = false;
     ldpc_params p{};
     uint64_t seed = 1;
 };
@@ -89,11 +99,12 @@ void worker(int dev, const ldpc_code *h, const Opt &o, double sigma, Totals &tot
     uint32_t table[64];
     CHECK(ldpc_awgn_i8_table(sigma, 8, 31, table));
     int8_t *d_llr;
+    float *d_y = nullptr;   // the float chains' channel output
     uint8_t *d_hard, *d_cw = nullptr;
     unsigned long long *d_cnt;
     (void)hipSetDevice(dev);
     if (hipMalloc(&d_llr, (size_t)o.batch * n) || hipMalloc(&d_hard, (size_t)o.batch * n) ||
-        hipMalloc(&d_cnt, 16)) {
+        hipMalloc(&d_cnt, 16) || ((o.f32 || o.f32q) && hipMalloc(&d_y, (size_t)o.batch * n * sizeof(float)))) {
         fprintf(stderr, "hipMalloc failed\n");
         exit(1);
     }
@@ -122,9 +133,20 @@ void worker(int dev, const ldpc_code *h, const Opt &o, double sigma, Totals &tot
             if (genc) CHECK(ldpc_encode_async(ctx, stream, d_info, d_cw, o.batch));
             else CHECK(ldpc_dvbs2_encode_async(ctx, stream, d_info, d_cw, o.batch));
         }
-        CHECK(ldpc_awgn_i8_async(ctx, stream, d_llr, o.batch, first, o.seed, table, d_cw));
-        CHECK(ldpc_decode_i8_async(ctx, stream, d_llr, d_hard, nullptr, nullptr, o.batch, o.iter, &o.p));
-        CHECK(ldpc_count_errors_async(ctx, stream, d_hard, o.batch, k, d_cw, d_cnt));
+        if (o.f32) {
+            CHECK(ldpc_awgn_f32_async(ctx, stream, d_y, o.batch, first, o.seed, sigma, 1.0, 1.0, d_cw));
+            CHECK(ldpc_decode_f32_count_async(ctx, stream, d_y, d_hard, nullptr, nullptr, o.batch, o.iter, &o.p, k,
+                                              d_cw, d_cnt));
+        } else {
+            if (o.f32q) {
+                CHECK(ldpc_awgn_f32_async(ctx, stream, d_y, o.batch, first, o.seed, sigma, 1.0, 1.0, d_cw));
+                CHECK(ldpc_quantize_f32_i8_async(ctx, stream, d_y, d_llr, (long)o.batch * n, 8, -31, 31));
+            } else {
+                CHECK(ldpc_awgn_i8_async(ctx, stream, d_llr, o.batch, first, o.seed, table, d_cw));
+            }
+            CHECK(ldpc_decode_i8_async(ctx, stream, d_llr, d_hard, nullptr, nullptr, o.batch, o.iter, &o.p));
+            CHECK(ldpc_count_errors_async(ctx, stream, d_hard, o.batch, k, d_cw, d_cnt));
+        }
         unsigned long long c[2];
         if (hipMemcpyAsync(c, d_cnt, 16, hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess ||
             hipStreamSynchronize((hipStream_t)stream) != hipSuccess) {
@@ -136,6 +158,7 @@ void worker(int dev, const ldpc_code *h, const Opt &o, double sigma, Totals &tot
         tot.frames += o.batch;
     }
     (void)hipFree(d_llr);
+    if (d_y) (void)hipFree(d_y);
     (void)hipFree(d_hard);
     (void)hipFree(d_cnt);
     if (d_cw) (void)hipFree(d_cw);
@@ -170,6 +193,9 @@ int main(int argc, char **argv)
         else if (a == "-gencoder") o.gencoder = true;
         else if (a == "-fresh") o.fresh = true;
         else if (a == "-et") o.p.early_term = 1;
+        else if (a == "-f32") o.f32 = true;
+        else if (a == "-f32q") o.f32q = true;
+        else if (a == "-beta") o.p.beta = (float)atof(nxt());
         else {
             fprintf(stderr, "unknown option %s\n", a.c_str());
             return 2;
@@ -178,6 +204,11 @@ int main(int argc, char **argv)
     if (o.encoder && o.gencoder) {
         fprintf(stderr, "usage: -encoder (DVB-S2 IRA encoder) and -gencoder (general encoder, any code) exclude "
                         "each other\n");
+        return 2;
+    }
+    if (o.f32 && o.f32q) {
+        fprintf(stderr, "usage: -f32 (float channel -> float decode) and -f32q (float channel -> quantise -> int8 "
+                        "decode) exclude each other\n");
         return 2;
     }
     if (o.fresh && !o.encoder && !o.gencoder) {
@@ -211,8 +242,10 @@ int main(int argc, char **argv)
         if (genc) CHECK(ldpc_encode(genc, info.data(), pool.data(), pool_n));
         else CHECK(ldpc_dvbs2_encode(h, info.data(), pool.data(), pool_n));
     }
-    printf("(II) code %s N=%d K=%d E=%d | %s | iters %d | batch %d x %d GPU(s)\n", o.code.c_str(), n, k, e,
-           o.p.algo == LDPC_ALGO_NMS ? "NMS" : (o.p.algo == LDPC_ALGO_MS ? "MS" : "OMS"), o.iter, o.batch, o.gpus);
+    const char *chain = o.f32 ? "f32" : (o.f32q ? "f32q" : "i8");
+    printf("(II) code %s N=%d K=%d E=%d | %s | chain %s | iters %d | batch %d x %d GPU(s)\n", o.code.c_str(), n, k, e,
+           o.p.algo == LDPC_ALGO_NMS ? "NMS" : (o.p.algo == LDPC_ALGO_MS ? "MS" : "OMS"), chain, o.iter, o.batch,
+           o.gpus);
     for (double eb = o.min; eb <= o.max + 1e-9; eb += o.pas) {
         const double sigma = ldpc_awgn_sigma(eb, (double)k / n);
         Totals tot;
@@ -230,8 +263,8 @@ int main(int argc, char **argv)
                "BE/FE = %.1f | RUNTIME = %.2fs\n",
                eb, ber, fer, (double)fr * k / sec / 1e6, fr, fe, be, fe ? (double)be / fe : 0.0, sec);
         printf("{\"ebn0\": %.3f, \"sigma\": %.6f, \"frames\": %ld, \"frame_errors\": %ld, \"bit_errors\": %ld, "
-               "\"ber\": %.6e, \"fer\": %.6e, \"coded_mbps\": %.3f}\n",
-               eb, sigma, fr, fe, be, ber, fer, mbps);
+               "\"ber\": %.6e, \"fer\": %.6e, \"coded_mbps\": %.3f, \"chain\": \"%s\"}\n",
+               eb, sigma, fr, fe, be, ber, fer, mbps, chain);
         fflush(stdout);
     }
     ldpc_encoder_destroy(genc);

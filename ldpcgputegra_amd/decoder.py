@@ -211,6 +211,16 @@ class Decoder:
         self._on_stream(stream, lambda s: _lib.check(_lib.lib().ldpc_awgn_i8_async(
             self._ctx, s, self._ptr(llr), llr.shape[0], first_cw, seed, t.ctypes.data, self._ptr(codeword))), self.device)
 
+    def awgn_f32_device(self, y, first_cw, seed, sigma, amp=1.0, normalize=False, codeword=None, stream=None):
+        """Fill y (float32 [batch, N], contiguous, 4-byte aligned) with the float
+        channel's samples of codewords first_cw .. (channel.awgn_f32_host's
+        generator, bit for bit, on the device)."""
+        assert y.is_contiguous() and y.numel() == y.shape[0] * self.code.n
+        norm = 2.0 / (sigma * sigma) if normalize else 1.0
+        self._on_stream(stream, lambda s: _lib.check(_lib.lib().ldpc_awgn_f32_async(
+            self._ctx, s, self._ptr(y), y.shape[0], first_cw, seed, float(sigma), float(amp), float(norm),
+            self._ptr(codeword))), self.device)
+
     def info_bits_device(self, info, first_cw, seed, stream=None):
         """Fill info (uint8 [batch, K]) with the information bits of codewords
         first_cw .. (channel.info_bits_host's generator, on the device)."""
