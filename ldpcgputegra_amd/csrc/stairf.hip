@@ -370,7 +370,8 @@ int stairf_width(const StairfCode &sc, int stride)
 {
     const char *e = getenv("LDPC_STAIRF_S");
     const int want = (e && *e) ? atoi(e) : stride >= 8192 ? 2 : stride >= 4096 ? 4 : stride >= 2048 ? 8 : 16;
-    for (int S : {want, 8, 4, 16})
+    // (2 last: a code whose min_hazard leaves only the narrowest table is valid, so some width must be found)
+    for (int S : {want, 8, 4, 16, 2})
         if ((S == 2 || S == 4 || S == 8 || S == 16) && sc.d_tab[s_index(S)]) return S;
     return 0;
 }

@@ -23,12 +23,10 @@ def checks(t):
     return out
 
 
-@pytest.mark.parametrize("code", ["dvbs2_r1_2", "dvbs2_r2_3"])
-@pytest.mark.parametrize("S,R,dist", [(24, 3, 1), (28, 3, 1), (28, 4, 1), (32, 3, 1), (24, 3, 2)])
-def test_coop_plan_rules(code, S, R, dist):
-    t = load_table(code)
-    plan = Code(code).coop_plan(S, R, dist)
-    assert plan is not None
+def check_coop_plan(t, plan, S, R, dist):
+    """The three rules above on the plan of table t (any staircase table:
+    test_struct_domain_cpu.py runs synthetic ones through it too); returns the
+    per-window sets of information variables."""
     ch = checks(t)
     M, D0 = t.m, t.groups[0][0]
     X = D0 - 2
@@ -71,6 +69,17 @@ def test_coop_plan_rules(code, S, R, dist):
                     nf += 1
                 last[v] = u
     assert nf == plan["n_fwd"]
+    return wvars
+
+
+@pytest.mark.parametrize("code", ["dvbs2_r1_2", "dvbs2_r2_3"])
+@pytest.mark.parametrize("S,R,dist", [(24, 3, 1), (28, 3, 1), (28, 4, 1), (32, 3, 1), (24, 3, 2)])
+def test_coop_plan_rules(code, S, R, dist):
+    t = load_table(code)
+    plan = Code(code).coop_plan(S, R, dist)
+    assert plan is not None
+    check_coop_plan(t, plan, S, R, dist)
+    M, X, nw = t.m, t.groups[0][0] - 2, len(plan["windows"])
     # windows are mostly full and forwarding is rare
     assert (M - 1) / (nw * S) > (0.85 if dist == 1 else 0.8)
     assert plan["n_fwd"] < 0.05 * (M * X)
