@@ -333,6 +333,88 @@ LDPC_DEV uint32_t old_msg2(const uint32_t (&MA)[NMA], const MsgTab &t, const PkK
     return old_msg<J & 7>(MA[J >> 3], t, K.m3, K.c4);
 }
 
+// ---- the check arithmetic of Slab3::pre / post that touches no memory, as
+// functions of its own (tests/cpp/coop3_arith_probe.hip runs them against a
+// scalar reference over their whole input domain)
+
+// running min1 / min2 over |c| (R pairs): edge J of a check's first group.
+// a <= R(127), so the first edge is min1 and the second needs no min with min2
+template <int J>
+LDPC_DEV void min_track(uint32_t &min1, uint32_t &min2, uint32_t aj)
+{
+    if constexpr (J == 0) {
+        min1 = aj;
+    } else if constexpr (J == 1) {
+        min2 = pk_max(min1, aj);
+        min1 = pk_min(min1, aj);
+    } else {
+        min2 = pk_max(min1, pk_min(aj, min2));
+        min1 = pk_min(min1, aj);
+    }
+}
+// the two interleaved chains (even / odd edges) of the chunked pre merged: the
+// exact smallest and second smallest of the union, ties included
+LDPC_DEV void min_merge2(const uint32_t (&m1)[2], const uint32_t (&m2)[2], uint32_t &min1, uint32_t &min2)
+{
+    min1 = pk_min(m1[0], m1[1]);
+    min2 = pk_min(pk_max(m1[0], m1[1]), pk_min(m2[0], m2[1]));
+}
+
+// a check's chain constants A, B, EPS, COV, L, H in value form (R >> 8, C >> 8), both codewords at once
+// first-group check: cor = the o edge's contribution (R pair, clamped at
+// R(-127)), mx = the x edge's old message (C pair), min1 = the smallest |c| of
+// the information edges (R pair, not yet clipped at msg_max), kb = their sign
+// parity with the odd-degree flip (sign bits), offp = the offset per half
+template <bool NMS>
+LDPC_DEV void chain_consts(uint32_t cor, uint32_t mx, uint32_t min1, uint32_t kb, const PkK &K, uint32_t fk,
+                           uint32_t offp, uint32_t &A, uint32_t &B, uint32_t &EPS, uint32_t &COV, uint32_t &L,
+                           uint32_t &H)
+{
+    COV = pk_ashr8(cor);
+    const uint32_t EM = pk_sra15(kb);   // EM: -1 where eps = -1
+    uint32_t TV;                        // cst over the info edges (value form)
+    if constexpr (NMS) {
+        TV = nms_v(pk_min(min1, K.rmm), fk);
+        EPS = pk_sub(fk ^ EM, EM);                                  // eps * f
+        const uint32_t efm = pk_mul_lo(pk_ashr8(mx), EPS);          // eps * f * m_x
+        A = pk_sub(pk_shl5(COV), efm);                            // 32 c_o - eps f m_x
+        B = pk_add(A, 0x001F001Fu);
+    } else {
+        TV = pk_ashr8(pk_max(pk_sub(pk_min(min1, K.rmm), K.coff), 0u));   // coff = C(off) + 255: C form
+        EPS = EM | 0x00010001u;
+        const uint32_t base = pk_sub(COV, pk_sub(pk_ashr8(mx) ^ EM, EM));   // c_o - eps * m_x
+        A = pk_sub(base, offp);
+        B = pk_add(base, offp);
+    }
+    L = pk_max(pk_sub(COV, TV), VNEG127);
+    H = pk_min(pk_add(COV, TV), V127);
+}
+// FZ: converged codewords (halves fm): L = H = V[p_i] as read (vo: R pair), the step returns it
+LDPC_DEV void chain_freeze(uint32_t fm, uint32_t vo, uint32_t &L, uint32_t &H)
+{
+    const uint32_t VO = pk_ashr8(vo);
+    L = bfi(fm, VO, L);
+    H = bfi(fm, VO, H);
+}
+// the post's finish of a first-group check: the x edge's contribution from
+// the chain input xr, min1 / min2 over all edges, the constants (C form) and
+// eps * constants.  sacc = the sign parity of the other edges, ODD = the
+// odd-degree flip
+template <bool NMS, bool ODD>
+LDPC_DEV void post_finish(uint32_t xr, uint32_t mx, uint32_t mn1, uint32_t mn2, uint32_t sacc0, const PkK &K,
+                          uint32_t fk, uint32_t &cx, uint32_t &ax, uint32_t &min1, uint32_t &min2, uint32_t &k1,
+                          uint32_t &k2, uint32_t &e1, uint32_t &e2)
+{
+    cx = pk_sub_sat(xr, mx);   // unclamped, as the info edges' (new_v)
+    ax = abs_sat(cx, K.c510);
+    const uint32_t sacc = sacc0 ^ cx;
+    min2 = pk_max(mn1, pk_min(ax, mn2)), min1 = pk_min(ax, mn1);
+    k1 = NMS ? nms_c(pk_min(min2, K.rmm), fk)
+                            : pk_max(pk_sub(pk_min(min2, K.rmm), K.coff), 0u);   // C(max(min - off, 0))
+    k2 = NMS ? nms_c(pk_min(min1, K.rmm), fk)
+                            : pk_max(pk_sub(pk_min(min1, K.rmm), K.coff), 0u);
+    signed_csts(k1, k2, sacc ^ (ODD ? SIGNS : 0u), e1, e2);
+}
 template <int D0, int WS, int R, bool NMS = false, bool LEAN = false, bool KA_ = G3<D0>::KEEP_AD>
 struct Slab3 {
     using SM = Smem3<D0, WS, R>;
@@ -506,6 +588,9 @@ struct Slab3 {
             // 0x8000 below R(-128) included): the post uses only their sign
             // and |c| (abs_sat caps it at R(127) as the reference's clamp does)
             if constexpr (XL < LDPC_C3_PRE_CHUNK_X) {
+                // this path applies no sink(): every two-lanes-per-check degree takes the chunked one
+                static_assert(!G3<D0>::HALF || G3<D0>::XH >= LDPC_C3_PRE_CHUNK_X,
+                              "HALF: the unchunked pre does not neutralise sink entries");
                 static_for<0, XL>([&](auto jc) __attribute__((always_inline)) {
                     constexpr int J = decltype(jc)::value;
                     const uint32_t c = pk_sub_sat(v[J], old_msg2<J>(in.ma, t, K));
@@ -513,15 +598,7 @@ struct Slab3 {
                     s.c[J] = c;
                     if constexpr (!LEAN) s.a[J] = aj;
                     sacc ^= c;
-                    if constexpr (J == 0) {   // a <= R(127): the first edge is min1
-                        min1 = aj;
-                    } else if constexpr (J == 1) {
-                        min2 = pk_max(min1, aj);
-                        min1 = pk_min(min1, aj);
-                    } else {
-                        min2 = pk_max(min1, pk_min(aj, min2));
-                        min1 = pk_min(min1, aj);
-                    }
+                    min_track<J>(min1, min2, aj);   // a <= R(127): the first edge is min1
                 });
             } else {
                 // many info edges: contributions in stage-major chunks (as the
@@ -552,12 +629,10 @@ struct Slab3 {
                     __builtin_amdgcn_sched_barrier(0);
                     static_for<0, E>([&](auto ec) __attribute__((always_inline)) {
                         constexpr int e = decltype(ec)::value, h = (J0 + e) & 1;
-                        m2[h] = pk_max(m1[h], pk_min(aj[e], m2[h]));
-                        m1[h] = pk_min(m1[h], aj[e]);
+                        min_track<2>(m1[h], m2[h], aj[e]);
                     });
                 });
-                min1 = pk_min(m1[0], m1[1]);
-                min2 = pk_min(pk_max(m1[0], m1[1]), pk_min(m2[0], m2[1]));
+                min_merge2(m1, m2, min1, min2);
             }
             if constexpr (G::HALF) merge(min1, min2, sacc);   // the other half's info edges
             if constexpr (MP >= 0) __builtin_amdgcn_s_setprio(MP);   // mid-phase wave priority (fast periods)
@@ -567,37 +642,18 @@ struct Slab3 {
             s.c[XL] = cor;
             if constexpr (!LEAN) s.a[XL] = ao;
             s.sacc = sacc ^ cor;
-            s.mn2 = pk_max(min1, pk_min(ao, min2));
-            s.mn1 = pk_min(min1, ao);
+            s.mn1 = min1;
+            s.mn2 = min2;
+            min_track<2>(s.mn1, s.mn2, ao);
             const uint32_t mx = old_msg2<SX>(in.ma, t, K);
             s.mx = mx;
-            // chain constants in value form (R >> 8, C >> 8), both codewords at once
-            COV = pk_ashr8(cor);
-            const uint32_t EM = pk_sra15(kb);   // EM: -1 where eps = -1
-            uint32_t TV;                        // cst over the info edges (value form)
-            if constexpr (NMS) {
-                TV = nms_v(pk_min(min1, K.rmm), fk);
-                EPS = pk_sub(fk ^ EM, EM);                                    // eps * f
-                const uint32_t efm = pk_mul_lo(pk_ashr8(mx), EPS);            // eps * f * m_x
-                A = pk_sub(pk_shl5(COV), efm);                                // 32 c_o - eps f m_x
-                B = pk_add(A, 0x001F001Fu);
-            } else {
-                TV = pk_ashr8(pk_max(pk_sub(pk_min(min1, K.rmm), K.coff), 0u));   // coff = C(off) + 255: C form
-                EPS = EM | 0x00010001u;
-                const uint32_t base = pk_sub(COV, pk_sub(pk_ashr8(mx) ^ EM, EM));   // c_o - eps * m_x
-                A = pk_sub(base, a.offp);
-                B = pk_add(base, a.offp);
-            }
-            L = pk_max(pk_sub(COV, TV), VNEG127);
-            H = pk_min(pk_add(COV, TV), V127);
+            chain_consts<NMS>(cor, mx, min1, kb, K, fk, a.offp, A, B, EPS, COV, L, H);
             if constexpr (FZ) {   // converged codewords: L = H = V[p_i] as read, the step returns it
                 if constexpr (!FZ_REREAD) {
 #pragma unroll
                     for (int j = 0; j < X; j++) s.v[j] = v[j];
                 }
-                const uint32_t VO = pk_ashr8(v[XL]);
-                L = bfi(fm, VO, L);
-                H = bfi(fm, VO, H);
+                chain_freeze(fm, v[XL], L, H);
             }
         } else {
             // the tail check (later degree group: a = |min(c, msg_max)|,
@@ -614,8 +670,7 @@ struct Slab3 {
                 s.c[J] = c;
                 av(J) = aj;
                 sacc ^= c;
-                min2 = pk_max(min1, pk_min(aj, min2));
-                min1 = pk_min(min1, aj);
+                min_track<2>(min1, min2, aj);
             };
             static_for<0, XL>([&](auto jc) __attribute__((always_inline)) { tail_edge(jc, jc); });
             if constexpr (G::HALF) merge(min1, min2, sacc);   // the other half's info edges
@@ -716,16 +771,8 @@ struct Slab3 {
             return new_v<J & 7>(c, av, min1, e1, e2, MA[J >> 3], K.c510);
         };
         if constexpr (!TL) {
-            const uint32_t cx = pk_sub_sat(xr, s.mx);   // unclamped, as the info edges' (new_v)
-            const uint32_t ax = abs_sat(cx, K.c510);
-            const uint32_t sacc = s.sacc ^ cx;
-            const uint32_t min2 = pk_max(s.mn1, pk_min(ax, s.mn2)), min1 = pk_min(ax, s.mn1);
-            const uint32_t k1 = NMS ? nms_c(pk_min(min2, K.rmm), fk)
-                                    : pk_max(pk_sub(pk_min(min2, K.rmm), K.coff), 0u);   // C(max(min - off, 0))
-            const uint32_t k2 = NMS ? nms_c(pk_min(min1, K.rmm), fk)
-                                    : pk_max(pk_sub(pk_min(min1, K.rmm), K.coff), 0u);
-            uint32_t e1, e2;
-            signed_csts(k1, k2, sacc ^ ((D0 & 1) ? SIGNS : 0u), e1, e2);
+            uint32_t cx, ax, min1, min2, k1, k2, e1, e2;
+            post_finish<NMS, (D0 & 1) != 0>(xr, s.mx, s.mn1, s.mn2, s.sacc, K, fk, cx, ax, min1, min2, k1, k2, e1, e2);
             auto put_new = [&](auto jc, uint32_t n) __attribute__((always_inline)) {
                 constexpr int J = decltype(jc)::value;
                 const uint32_t ad = ad_of(g, s, J);

@@ -49,6 +49,7 @@ pk_add_sat = _pk(lambda x, y: _sat(x + y))   # v_pk_add_i16 ... clamp
 pk_sub = _pk(lambda x, y: x - y)             # v_pk_sub_i16 (wraps)
 pk_max = _pk(np.maximum)                     # v_pk_max_i16
 pk_min = _pk(np.minimum)                     # v_pk_min_i16
+pk_mul_lo = _pk(lambda x, y: x * y)          # v_pk_mul_lo_u16 (the low 16 bits: sign-agnostic)
 
 
 def pk_sra15(a):                             # v_pk_ashrrev_i16 15
@@ -102,9 +103,10 @@ def abs_sat(r):                              # |x| of R(x) or of the saturated 0
 
 def signed_csts(k1, k2, sacc, D):
     """eps * k1, eps * k2 (C form), eps = -1 where the sign parity of the
-    check's contributions (and the odd-degree flip) is odd."""
-    Pm = pk_sra15(sacc ^ (SIGNS if D & 1 else 0))
-    return pk_sub(k1 ^ Pm, Pm), pk_sub(k2 ^ Pm, Pm)
+    check's contributions (and the odd-degree flip) is odd: pk16.h's form,
+    a v_pk_mul_lo_u16 by +-1 per half."""
+    eps = pk_sra15(sacc ^ (SIGNS if D & 1 else 0)) | 0x00010001
+    return pk_mul_lo(k1, eps), pk_mul_lo(k2, eps)
 
 
 def new_v(j, c, a, min1, e1, e2, MA):
@@ -170,18 +172,23 @@ def kernel_check(vraw, MA, MB, off, mm, later):
 
 
 # ---- reference and pair helpers --------------------------------------------
-def ref_check(v, m, off, mm, later):
-    """SURVEY.md 8(a) per-check recurrence (the oracle's semantics) on [B, D]."""
+def ref_check(v, m, off, mm, later, factor=None):
+    """SURVEY.md 8(a) per-check recurrence (the oracle's semantics) on [B, D].
+    factor: NMS (row a5: min(|c|, msg_max) in every group, cst = (min *
+    factor) >> 5, no offset, no clip of the constant)."""
     B, D = v.shape
     c = np.maximum(np.clip(v - m, -128, 127), -127)
-    a = np.abs(np.minimum(c, mm)) if later else np.minimum(np.abs(c), mm)
+    a = np.abs(np.minimum(c, mm)) if later and factor is None else np.minimum(np.abs(c), mm)
     min1 = np.full(B, 127)
     min2 = np.full(B, 127)
     for j in range(D):
         min2 = np.minimum(min2, np.maximum(a[:, j], min1))
         min1 = np.minimum(min1, a[:, j])
-    cst1 = np.minimum(np.maximum(min2 - off, 0), mm)
-    cst2 = np.minimum(np.maximum(min1 - off, 0), mm)
+    if factor is None:
+        cst1 = np.minimum(np.maximum(min2 - off, 0), mm)
+        cst2 = np.minimum(np.maximum(min1 - off, 0), mm)
+    else:
+        cst1, cst2 = (min2 * factor) >> 5, (min1 * factor) >> 5
     par = ((c < 0).sum(axis=1) + D) & 1
     r = np.where(a == min1[:, None], cst1[:, None], cst2[:, None])
     mn = np.where((c < 0) ^ (par[:, None] == 1), -r, r)
