@@ -79,7 +79,22 @@ enum {
 enum {
     LDPC_ALGO_OMS = 0,     /* offset min-sum   (CDecoder_OMS_fixed_SSE) */
     LDPC_ALGO_NMS = 1,     /* normalised min-sum (CDecoder_NMS_fixed_SSE) */
-    LDPC_ALGO_MS = 2       /* plain min-sum == OMS with offset 0 */
+    LDPC_ALGO_MS = 2,      /* plain min-sum == OMS with offset 0 */
+    LDPC_ALGO_BP = 3       /* layered belief propagation (sum-product), float input only: the
+                              algorithm the three above approximate.  Its check update is the
+                              box-plus a [+] b = -2 atanh(tanh(a/2) tanh(b/2)) (negated: this
+                              decoder reads V > 0 as bit 1), chained forward / backward over the
+                              check's edges, with ln(1 + e^-x) written out in IEEE + - * so that
+                              host and device agree bit for bit (csrc/bp_math.h).
+                              beta is ignored.  Not scale-invariant as min-sum is: the input
+                              must be the true LLR 2y / sigma^2.  Int8 input: LDPC_EUNSUPPORTED
+                              (the reference has no fixed-point BP).  Runs on LDPC_KERNEL_LDS
+                              (the automatic choice where lds_f32 of ldpc_code_layer_info
+                              prefers it) and LDPC_KERNEL_GENERIC (any code); every other
+                              forced family is LDPC_EUNSUPPORTED.  The fast float families
+                              LDPC_KERNEL_LDSEP and LDPC_KERNEL_STAIRF have no BP yet, so a
+                              DVB-S2 code decodes BP on the generic kernel: correct, slow;
+                              ldpc_ctx_last_skipped names the family passed over */
 };
 
 typedef struct ldpc_code ldpc_code;
@@ -89,7 +104,7 @@ typedef struct {
     int algo;        /* LDPC_ALGO_*                                  default OMS */
     int offset;      /* int8 OMS offset (setOffset)                  default 1   */
     int factor;      /* int8 NMS factor, scaled by 1/32 (setFactor)  default 29  */
-    float beta;      /* float path: OMS offset or NMS factor         default 0.15*/
+    float beta;      /* float path: OMS offset or NMS factor (BP: unused) default 0.15*/
     int var_min;     /* setVarRange(min, max)                   default -127,127 */
     int var_max;
     int msg_min;     /* setMsgRange(min, max)                   default -31, 31  */
@@ -235,6 +250,14 @@ int ldpc_decode_i8(ldpc_ctx *ctx, const int8_t *llr, uint8_t *hard, int batch, i
                    const ldpc_params *p);
 int ldpc_decode_f32(ldpc_ctx *ctx, const float *llr, uint8_t *hard, int batch, int n_iter,
                     const ldpc_params *p);
+/* ldpc_decode_f32 on a host context (device -1) with the two further outputs
+ * of the device entry points: soft [batch][N], the final V per bit, and
+ * iters_used [batch] (either may be NULL).  It is what the GPU kernels' soft
+ * output and iteration counts are compared to, bit for bit, without a GPU in
+ * the reference.  A GPU context is LDPC_EUNSUPPORTED: ldpc_decode_f32_async
+ * returns both there.  (Replaces no reference interface.) */
+int ldpc_decode_f32_soft(ldpc_ctx *ctx, const float *llr, uint8_t *hard, float *soft, int32_t *iters_used,
+                         int batch, int n_iter, const ldpc_params *p);
 
 /* Host buffers, asynchronous: enqueue H2D(llr) -> decode -> D2H(hard) on
  * hip_stream (NULL: the null stream) and return -- the reference's "W streams
@@ -296,6 +319,19 @@ int ldpc_decode_f32_async(ldpc_ctx *ctx, void *hip_stream, const float *d_llr, u
 int ldpc_decode_i8_nm_async(ldpc_ctx *ctx, void *hip_stream, const int8_t *d_llr, size_t ld, uint8_t *d_hard,
                             int8_t *d_soft, int32_t *d_iters_used, int batch, int n_iter,
                             const ldpc_params *p);
+
+/* out[i] = a[i] [+] b[i], the box-plus of LDPC_ALGO_BP alone (csrc/bp_math.h):
+ * the only way to look at it outside a decode.  _host runs on the CPU and
+ * needs no context; _async on the device of a GPU context, asynchronous on
+ * hip_stream (NULL: the null stream), device buffers of `count` floats, bit for
+ * bit the host's results.  count = 0 is LDPC_OK and touches nothing (the
+ * pointers may then be NULL, as for the quantiser), a NULL pointer with
+ * count > 0 or a negative count LDPC_EINVAL, a host context LDPC_EUNSUPPORTED
+ * for _async.  Finite inputs only.  (Introspection for tests; replaces no
+ * reference interface.) */
+int ldpc_boxplus_f32_host(const float *a, const float *b, float *out, long count);
+int ldpc_boxplus_f32_async(ldpc_ctx *ctx, void *hip_stream, const float *d_a, const float *d_b, float *d_out,
+                           long count);
 
 /* ---- mixed-rate batches (BASELINE config 5) ---------------------------- */
 /* A batch whose codewords use different codes of equal length N (e.g. the

@@ -6,13 +6,13 @@ The compute path is the HIP library ``libldpc_mi355x.so`` (C-ABI in
 include/ldpc_mi355x.h); this package is its host-side binding.
 """
 from . import _lib
-from ._lib import ALGO_MS, ALGO_NMS, ALGO_OMS, LdpcError, default_params
+from ._lib import ALGO_BP, ALGO_MS, ALGO_NMS, ALGO_OMS, LdpcError, default_params
 from .codes import Code, Encoder, Table, available, load_table
 from .decoder import (CDecoder, CDecoder_NMS_fixed_MI355X, CDecoder_OMS_fixed_MI355X, CreateDecoder, Decoder,
-                      param_decoder, pinned_empty)
+                      boxplus_host, param_decoder, pinned_empty)
 
 __all__ = [
-    "ALGO_MS", "ALGO_NMS", "ALGO_OMS", "LdpcError", "default_params", "Code", "Encoder", "Table", "available",
+    "ALGO_BP", "ALGO_MS", "ALGO_NMS", "ALGO_OMS", "LdpcError", "default_params", "Code", "Encoder", "Table", "available",
     "load_table", "CDecoder", "CDecoder_OMS_fixed_MI355X", "CDecoder_NMS_fixed_MI355X", "CreateDecoder",
-    "Decoder", "param_decoder", "pinned_empty",
+    "Decoder", "boxplus_host", "param_decoder", "pinned_empty",
 ]

@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LDPC_MI355X_LIB") or os.path.join(_HERE, "libldpc_mi355x.so")
 
 LDPC_OK, LDPC_EINVAL, LDPC_EUNSUPPORTED, LDPC_EDEVICE, LDPC_ENOMEM, LDPC_EIO = 0, -1, -2, -3, -4, -5
-ALGO_OMS, ALGO_NMS, ALGO_MS = 0, 1, 2
+ALGO_OMS, ALGO_NMS, ALGO_MS, ALGO_BP = 0, 1, 2, 3
 
 
 def source_hash():
@@ -93,6 +93,9 @@ SIGNATURES = {
     "ldpc_ctx_kernel_time": (I, [P, C.POINTER(C.c_double), C.POINTER(I), I]),
     "ldpc_decode_i8": (I, [P, P, P, I, I, C.POINTER(ldpc_params)]),
     "ldpc_decode_f32": (I, [P, P, P, I, I, C.POINTER(ldpc_params)]),
+    "ldpc_decode_f32_soft": (I, [P, P, P, P, P, I, I, C.POINTER(ldpc_params)]),
+    "ldpc_boxplus_f32_host": (I, [P, P, P, C.c_long]),
+    "ldpc_boxplus_f32_async": (I, [P, P, P, P, P, C.c_long]),
     "ldpc_decode_i8_async": (I, [P, P, P, P, P, P, I, I, C.POINTER(ldpc_params)]),
     "ldpc_decode_f32_async": (I, [P, P, P, P, P, P, I, I, C.POINTER(ldpc_params)]),
     "ldpc_decode_i8_nm_async": (I, [P, P, P, C.c_size_t, P, P, P, I, I, C.POINTER(ldpc_params)]),

@@ -343,7 +343,7 @@ static int decode_host(ldpc_ctx *c, const void *llr, uint8_t *hard, int batch, i
     if (rc != LDPC_OK || batch == 0) return rc;
     if (c->device < 0) {   // host context: the CPU decoder (host.cpp)
         c->last_kernel = LDPC_KERNEL_HOST;
-        return is_float ? host_decode_f32(c->code, (const float *)llr, hard, batch, n_iter, p)
+        return is_float ? host_decode_f32(c->code, (const float *)llr, hard, nullptr, nullptr, batch, n_iter, p)
                         : host_decode_i8(c->code, (const int8_t *)llr, hard, batch, n_iter, p);
     }
     HIP_TRY(hipSetDevice(c->device));
@@ -512,6 +512,21 @@ extern "C" int ldpc_decode_f32(ldpc_ctx *c, const float *llr, uint8_t *hard, int
                                const ldpc_params *p)
 {
     return decode_host(c, llr, hard, batch, n_iter, p, true);
+}
+
+// the host decoder's float decode with the outputs the device entry points
+// have: what a test compares the kernels' soft output and iteration counts to
+extern "C" int ldpc_decode_f32_soft(ldpc_ctx *c, const float *llr, uint8_t *hard, float *soft, int32_t *iters_used,
+                                    int batch, int n_iter, const ldpc_params *p)
+{
+    if (!c || ((!llr || !hard) && batch > 0)) return ldpc_set_error(LDPC_EINVAL, "NULL ctx/llr/hard");
+    const int rc = check_params(c, batch, n_iter, p, true);
+    if (rc != LDPC_OK || batch == 0) return rc;
+    if (c->device >= 0)
+        return ldpc_set_error(LDPC_EUNSUPPORTED, "ldpc_decode_f32_soft takes a host context (device -1); a GPU "
+                              "context returns soft output through ldpc_decode_f32_async");
+    c->last_kernel = LDPC_KERNEL_HOST;
+    return host_decode_f32(c->code, llr, hard, soft, iters_used, batch, n_iter, p);
 }
 
 extern "C" int ldpc_awgn_i8_async(ldpc_ctx *c, void *s, int8_t *d_llr, int batch, uint64_t first_cw, uint64_t seed,

@@ -12,8 +12,11 @@ int check_params(const ldpc_ctx *c, int batch, int n_iter, const ldpc_params *p,
         return ldpc_set_error(LDPC_EINVAL, "batch %d outside [0, max_batch=%d]", batch, c->max_batch);
     if (n_iter < 0) return ldpc_set_error(LDPC_EINVAL, "n_iter < 0");
     if (!p) return ldpc_set_error(LDPC_EINVAL, "params NULL");
-    if (p->algo < 0 || p->algo > 2) return ldpc_set_error(LDPC_EINVAL, "algo %d", p->algo);
+    if (p->algo < 0 || p->algo > LDPC_ALGO_BP) return ldpc_set_error(LDPC_EINVAL, "algo %d", p->algo);
     if (!is_float) {
+        if (p->algo == LDPC_ALGO_BP)
+            return ldpc_set_error(LDPC_EUNSUPPORTED, "belief propagation takes float input (the reference has no "
+                                  "fixed-point BP)");
         // CDecoder_OMS_fixed_SSE::decode / CDecoder_NMS_fixed_SSE::decode exit
         // unless vSAT_POS_VAR == 127 (OMS .cpp:116-119, NMS .cpp:119-122)
         if (p->var_max != 127)
@@ -61,6 +64,16 @@ static int pick_kernel(ldpc_ctx *c, const ldpc_params *p, bool is_float, int str
     const ldpc_code *h = c->code;
     const bool automatic = c->kernel == LDPC_KERNEL_AUTO;
     const bool sf = family_fits(c, LDPC_KERNEL_STAIRF) && stairf_stride_ok(c->stairf, h->n, stride);
+    if (p->algo == LDPC_ALGO_BP) {   // float only (check_params); bp.hip has the LDS-resident and the any-H kernel
+        if (c->kernel == LDPC_KERNEL_LDS) return lds_applicable(h, c->lds, true) ? LDPC_KERNEL_LDS : -1;
+        if (c->kernel == LDPC_KERNEL_GENERIC) return LDPC_KERNEL_GENERIC;
+        if (!automatic) return -1;
+        if (ldsep_applicable(h, c->lds, true))
+            c->last_skipped = LDPC_KERNEL_LDSEP;
+        else if (sf)
+            c->last_skipped = LDPC_KERNEL_STAIRF;
+        return lds_preferred(h, c->lds, true) ? LDPC_KERNEL_LDS : LDPC_KERNEL_GENERIC;
+    }
     switch (c->kernel) {
     case LDPC_KERNEL_LDS: return lds_applicable(h, c->lds, is_float) ? LDPC_KERNEL_LDS : -1;
     case LDPC_KERNEL_LDSEP: return ldsep_applicable(h, c->lds, is_float) ? LDPC_KERNEL_LDSEP : -1;
@@ -265,6 +278,9 @@ static int decode_lds_resident(ldpc_ctx *c, Scratch &sc, hipStream_t s, int kern
     rc = profiled(c, s, &lr, [&] {
         if (kern == LDPC_KERNEL_LDSEP)
             return launch_ldsep(c->lds, h, (const float *)d_llr, rq.d_hard, (float *)rq.d_soft, batch, rq.n_iter, L, s);
+        if (L.algo == LDPC_ALGO_BP)
+            return launch_bp_lds(c->lds, h, (const float *)d_llr, rq.d_hard, (float *)rq.d_soft, L, s,
+                                 &c->last_lds_lanes);
         return launch_lds(c->lds, h, d_llr, rq.d_hard, rq.d_soft, batch, rq.n_iter, L, s, &c->last_lds_lanes,
                           &c->last_lds_split);
     });
@@ -352,7 +368,7 @@ static int decode_in_scratch(ldpc_ctx *c, Scratch &sc, hipStream_t s, int kern, 
         case LDPC_KERNEL_STAIRF: return launch_stairf(L, c->stairf, s);
         case LDPC_KERNEL_WINDOWED2: return launch_windowed2(L, c->w16, s);
         case LDPC_KERNEL_WINDOWED: return launch_windowed(L, c->wcode, s);
-        default: return launch_generic(L, s);
+        default: return L.algo == LDPC_ALGO_BP ? launch_bp_generic(L, s) : launch_generic(L, s);
         }
     });
     if (rc != LDPC_OK) return rc;

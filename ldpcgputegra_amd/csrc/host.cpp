@@ -17,6 +17,7 @@
 #include <thread>
 #include <vector>
 
+#include "bp_math.h"
 #include "host.h"
 #include "host_simd.h"
 
@@ -145,19 +146,31 @@ void decode_block_i8(const ldpc_code *h, const int8_t *llr, uint8_t *hard, int n
         for (int i = 0; i < n; i++) hard[(size_t)l * n + i] = s.v[(size_t)i * W + l] > 0;   // CTools.cpp:370
 }
 
-// one codeword, float (the same schedule; SURVEY.md §8(a) float variant)
-void decode_one_f32(const ldpc_code *h, const float *llr, uint8_t *hard, int iters, int algo, float beta, bool early,
+// one codeword, float (the same schedule; SURVEY.md §8(a) float variant);
+// returns the iterations run, V holds the soft output
+int decode_one_f32(const ldpc_code *h, const float *llr, uint8_t *hard, int iters, int algo, float beta, bool early,
                     std::vector<float> &V, std::vector<float> &msg)
 {
     V.assign(llr, llr + h->n);
     msg.assign((size_t)h->e, 0.0f);
     float c[64], a[64];
-    for (int it = 0; it < iters; it++) {
+    int it = 0;
+    while (it < iters) {
         size_t e0 = 0;
         for (int i = 0; i < h->m; i++) {
             const int d = h->check_deg[i];
             const uint32_t *ev = &h->edge_var[h->check_start[i]];
             float *mp = &msg[e0];
+            if (algo == LDPC_ALGO_BP) {   // sum-product: bp_math.h, the definition of DESIGN.md §3
+                for (int j = 0; j < d; j++) c[j] = a[j] = V[ev[j]] - mp[j];
+                bp_check(d, c, a);
+                for (int j = 0; j < d; j++) {
+                    mp[j] = a[j];
+                    V[ev[j]] = c[j] + a[j];
+                }
+                e0 += (size_t)d;
+                continue;
+            }
             int sign = d & 1;
             float min1 = __builtin_huge_valf(), min2 = min1;
             for (int j = 0; j < d; j++) {
@@ -178,6 +191,7 @@ void decode_one_f32(const ldpc_code *h, const float *llr, uint8_t *hard, int ite
             }
             e0 += (size_t)d;
         }
+        it++;
         if (early) {
             bool ok = true;
             for (int i = 0; i < h->m && ok; i++) {
@@ -189,6 +203,7 @@ void decode_one_f32(const ldpc_code *h, const float *llr, uint8_t *hard, int ite
         }
     }
     for (int i = 0; i < h->n; i++) hard[i] = V[i] > 0.0f;
+    return it;
 }
 
 int host_threads_for(int units)
@@ -242,15 +257,26 @@ int host_decode_i8(const ldpc_code *h, const int8_t *llr, uint8_t *hard, int bat
     return LDPC_OK;
 }
 
-int host_decode_f32(const ldpc_code *h, const float *llr, uint8_t *hard, int batch, int n_iter, const ldpc_params *p)
+// a [+] b of bp_math.h, element by element (introspection: the box-plus of the BP decoders alone)
+extern "C" int ldpc_boxplus_f32_host(const float *a, const float *b, float *out, long count)
 {
-    const int algo = p->algo == LDPC_ALGO_NMS ? LDPC_ALGO_NMS : LDPC_ALGO_OMS;
+    if (count < 0 || (count > 0 && (!a || !b || !out))) return ldpc_set_error(LDPC_EINVAL, "boxplus args");
+    for (long i = 0; i < count; i++) out[i] = bp_boxplus(a[i], b[i]);
+    return LDPC_OK;
+}
+
+int host_decode_f32(const ldpc_code *h, const float *llr, uint8_t *hard, float *soft, int32_t *iters_used, int batch,
+                    int n_iter, const ldpc_params *p)
+{
+    const int algo = (p->algo == LDPC_ALGO_NMS || p->algo == LDPC_ALGO_BP) ? p->algo : LDPC_ALGO_OMS;
     const float beta = p->algo == LDPC_ALGO_MS ? 0.0f : p->beta;
     const int nt = host_threads_for(std::max(batch, 1));
     std::vector<std::vector<float>> V((size_t)nt), M((size_t)nt);
     parallel_units(batch, [&](int b, int k) {
-        decode_one_f32(h, llr + (size_t)b * h->n, hard + (size_t)b * h->n, n_iter, algo, beta, p->early_term != 0,
-                       V[k], M[k]);
+        const int it = decode_one_f32(h, llr + (size_t)b * h->n, hard + (size_t)b * h->n, n_iter, algo, beta,
+                                      p->early_term != 0, V[k], M[k]);
+        if (soft) std::memcpy(soft + (size_t)b * h->n, V[k].data(), sizeof(float) * (size_t)h->n);
+        if (iters_used) iters_used[b] = it;
     });
     return LDPC_OK;
 }

@@ -44,6 +44,8 @@ struct DecodeLaunch {
 };
 
 int launch_generic(const DecodeLaunch &L, hipStream_t s);
+// belief propagation in generic's layout (bp.hip; float only)
+int launch_bp_generic(const DecodeLaunch &L, hipStream_t s);
 
 // frame-major [batch][N] <-> node-major V[N][stride] (+ hard decision x > 0)
 int launch_quantize_f32_i8(const float *y, int8_t *q, long count, int factor, int sat_neg, int sat_pos,

@@ -11,7 +11,7 @@
 //   ldpc_sim -code dvbs2_r1_2 -min 0.8 -max 1.2 -pas 0.1 -iter 50 -fer 100
 //            [-batch 4096] [-frames 1000000] [-OMS 1 | -NMS 29 | -MS]
 //            [-encoder [-fresh] | -gencoder [-fresh]] [-et] [-gpus N] [-seed S]
-//            [-kernel K] [-f32 [-beta B] | -f32q]
+//            [-kernel K] [-f32 [-beta B] | -f32q | -BP]
 //
 // Three chains see the same noise (one u per element, the same first_cw and
 // seed scheme): the default draws the quantised int8 LLRs directly
@@ -21,7 +21,11 @@
 // -beta B is the float OMS offset or NMS factor, -OMS / -NMS / -MS choose the
 // algorithm, their int8 value is not used); -f32q is the reference's chain
 // stage by stage: float channel -> ldpc_quantize_f32_i8_async (8, +-31) -> the
-// int8 decode.  The JSON line names the chain ("i8", "f32", "f32q").
+// int8 decode.  The JSON line names the chain ("i8", "f32", "f32q") and the
+// algorithm.  -BP is the f32 chain with belief propagation (LDPC_ALGO_BP): the
+// yardstick curve of the three min-sum algorithms.  BP is not scale-invariant,
+// so its channel is drawn with norm = 2 / sigma^2 (true LLRs) where the other
+// -f32 runs keep 1.0; there is no int8 BP, so -BP with -f32q is a usage error.
 //
 // -encoder alone draws 64 codewords once on the host and replicates them over
 // every batch; -encoder -fresh draws new information bits and encodes them on
@@ -54,7 +58,7 @@ struct Opt {
     double min = 0.5, max = 3.0, pas = 0.1;
     int iter = 30, fer = 100, batch = 4096, gpus = 1, kernel = LDPC_KERNEL_AUTO;
     long frames = 1 << 20;
-    bool encoder = false, gencoder = false, fresh = false, f32 = false, f32q = false;
+    bool encoder = false, gencoder = false, fresh = false, f32 = false, f32q = false, bp = false;
     ldpc_params p{};
     uint64_t seed = 1;
 };
@@ -134,7 +138,8 @@ void worker(int dev, const ldpc_code *h, const Opt &o, double sigma, Totals &tot
             else CHECK(ldpc_dvbs2_encode_async(ctx, stream, d_info, d_cw, o.batch));
         }
         if (o.f32) {
-            CHECK(ldpc_awgn_f32_async(ctx, stream, d_y, o.batch, first, o.seed, sigma, 1.0, 1.0, d_cw));
+            const double norm = o.p.algo == LDPC_ALGO_BP ? 2.0 / (sigma * sigma) : 1.0;
+            CHECK(ldpc_awgn_f32_async(ctx, stream, d_y, o.batch, first, o.seed, sigma, 1.0, norm, d_cw));
             CHECK(ldpc_decode_f32_count_async(ctx, stream, d_y, d_hard, nullptr, nullptr, o.batch, o.iter, &o.p, k,
                                               d_cw, d_cnt));
         } else {
@@ -189,6 +194,7 @@ int main(int argc, char **argv)
         else if (a == "-OMS") { o.p.algo = LDPC_ALGO_OMS; o.p.offset = atoi(nxt()); }
         else if (a == "-NMS") { o.p.algo = LDPC_ALGO_NMS; o.p.factor = atoi(nxt()); }
         else if (a == "-MS") o.p.algo = LDPC_ALGO_MS;
+        else if (a == "-BP") o.bp = true;
         else if (a == "-encoder") o.encoder = true;
         else if (a == "-gencoder") o.gencoder = true;
         else if (a == "-fresh") o.fresh = true;
@@ -210,6 +216,15 @@ int main(int argc, char **argv)
         fprintf(stderr, "usage: -f32 (float channel -> float decode) and -f32q (float channel -> quantise -> int8 "
                         "decode) exclude each other\n");
         return 2;
+    }
+    if (o.bp) {   // belief propagation: the float chain, whatever -OMS / -NMS / -MS said
+        if (o.f32q) {
+            fprintf(stderr, "usage: -BP (belief propagation) is a float decode: it runs the -f32 chain and excludes "
+                            "-f32q and the int8 chain\n");
+            return 2;
+        }
+        o.f32 = true;
+        o.p.algo = LDPC_ALGO_BP;
     }
     if (o.fresh && !o.encoder && !o.gencoder) {
         fprintf(stderr, "usage: -fresh (new codewords every frame) needs -encoder\n");
@@ -243,9 +258,11 @@ int main(int argc, char **argv)
         else CHECK(ldpc_dvbs2_encode(h, info.data(), pool.data(), pool_n));
     }
     const char *chain = o.f32 ? "f32" : (o.f32q ? "f32q" : "i8");
+    const char *algo = o.p.algo == LDPC_ALGO_BP    ? "BP"
+                       : o.p.algo == LDPC_ALGO_NMS ? "NMS"
+                                                   : (o.p.algo == LDPC_ALGO_MS ? "MS" : "OMS");
     printf("(II) code %s N=%d K=%d E=%d | %s | chain %s | iters %d | batch %d x %d GPU(s)\n", o.code.c_str(), n, k, e,
-           o.p.algo == LDPC_ALGO_NMS ? "NMS" : (o.p.algo == LDPC_ALGO_MS ? "MS" : "OMS"), chain, o.iter, o.batch,
-           o.gpus);
+           algo, chain, o.iter, o.batch, o.gpus);
     for (double eb = o.min; eb <= o.max + 1e-9; eb += o.pas) {
         const double sigma = ldpc_awgn_sigma(eb, (double)k / n);
         Totals tot;
@@ -263,8 +280,8 @@ int main(int argc, char **argv)
                "BE/FE = %.1f | RUNTIME = %.2fs\n",
                eb, ber, fer, (double)fr * k / sec / 1e6, fr, fe, be, fe ? (double)be / fe : 0.0, sec);
         printf("{\"ebn0\": %.3f, \"sigma\": %.6f, \"frames\": %ld, \"frame_errors\": %ld, \"bit_errors\": %ld, "
-               "\"ber\": %.6e, \"fer\": %.6e, \"coded_mbps\": %.3f, \"chain\": \"%s\"}\n",
-               eb, sigma, fr, fe, be, ber, fer, mbps, chain);
+               "\"ber\": %.6e, \"fer\": %.6e, \"coded_mbps\": %.3f, \"chain\": \"%s\", \"algo\": \"%s\"}\n",
+               eb, sigma, fr, fe, be, ber, fer, mbps, chain, algo);
         fflush(stdout);
     }
     ldpc_encoder_destroy(genc);

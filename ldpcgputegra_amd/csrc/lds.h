@@ -35,3 +35,6 @@ int launch_ldsep(const LdsCode &lc, const ldpc_code *h, const float *llr, uint8_
 int launch_lds(const LdsCode &lc, const ldpc_code *h, const void *llr, uint8_t *hard, void *soft, int batch,
                int iters, const DecodeLaunch &L, hipStream_t s, int *lanes_per_codeword = nullptr,
                int *split = nullptr);
+// belief propagation on the same tables (bp.hip; float, one lane per check, never split)
+int launch_bp_lds(const LdsCode &lc, const ldpc_code *h, const float *llr, uint8_t *hard, float *soft,
+                  const DecodeLaunch &L, hipStream_t s, int *lanes_per_codeword = nullptr);

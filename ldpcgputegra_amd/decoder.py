@@ -39,6 +39,18 @@ def pinned_empty(shape, dtype):
     return np.frombuffer(buf, dtype=dt, count=int(np.prod(shape))).reshape(shape)
 
 
+def boxplus_host(a, b):
+    """a [+] b element by element (float32, same shape): the box-plus of
+    belief propagation (ALGO_BP) alone, on the CPU (``ldpc_boxplus_f32_host``,
+    csrc/bp_math.h).  Decoder.boxplus_device is its device twin, bit for bit."""
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    b = np.ascontiguousarray(b, dtype=np.float32)
+    assert a.shape == b.shape
+    out = np.empty(a.shape, dtype=np.float32)
+    _lib.check(_lib.lib().ldpc_boxplus_f32_host(a.ctypes.data, b.ctypes.data, out.ctypes.data, a.size))
+    return out
+
+
 class Decoder:
     """One C-ABI decoder context (device scratch for ``max_batch`` codewords)."""
 
@@ -140,6 +152,21 @@ class Decoder:
         _lib.check(_lib.lib().ldpc_decode_f32(self._ctx, llr.ctypes.data, hard.ctypes.data, B, n_iter, C.byref(p)))
         return hard
 
+    def decode_f32_soft(self, llr, n_iter, params=None):
+        """Host context (device=-1) only: (hard, soft, iters_used) of the float
+        decode -- the outputs decode_f32_device gives on a GPU context, here
+        from the host decoder (``ldpc_decode_f32_soft``)."""
+        llr = np.ascontiguousarray(llr, dtype=np.float32)
+        B = llr.shape[0] if llr.ndim == 2 else 1
+        assert llr.size == B * self.code.n
+        hard = np.empty((B, self.code.n), dtype=np.uint8)
+        soft = np.empty((B, self.code.n), dtype=np.float32)
+        iters = np.empty(B, dtype=np.int32)
+        p = params or _lib.default_params(algo=_lib.ALGO_MS)
+        _lib.check(_lib.lib().ldpc_decode_f32_soft(self._ctx, llr.ctypes.data, hard.ctypes.data, soft.ctypes.data,
+                                                   iters.ctypes.data, B, n_iter, C.byref(p)))
+        return hard, soft, iters
+
     # -- host buffers, asynchronous (H2D -> decode -> D2H queued on `stream`)
     def decode_i8_host_async(self, llr, hard, n_iter, params=None, stream=None):
         """Queue the decode of host (preferably pinned_empty) arrays llr -> hard
@@ -205,6 +232,14 @@ class Decoder:
         self._on_stream(stream, lambda s: _lib.check(_lib.lib().ldpc_decode_f32_async(
             self._ctx, s, self._ptr(llr), self._ptr(hard), self._ptr(soft), self._ptr(iters_used), B, n_iter,
             C.byref(p))), self.device)
+
+    def boxplus_device(self, a, b, out, stream=None):
+        """out = a [+] b element by element on the device (float32 tensors of
+        one size): boxplus_host's twin, bit for bit (``ldpc_boxplus_f32_async``)."""
+        assert a.is_contiguous() and b.is_contiguous() and out.is_contiguous()
+        assert a.numel() == b.numel() == out.numel()
+        self._on_stream(stream, lambda s: _lib.check(_lib.lib().ldpc_boxplus_f32_async(
+            self._ctx, s, self._ptr(a), self._ptr(b), self._ptr(out), a.numel())), self.device)
 
     def awgn_i8_device(self, llr, first_cw, seed, table, codeword=None, stream=None):
         t = np.ascontiguousarray(table, dtype=np.uint32)
