@@ -199,6 +199,11 @@ struct G3 {
 #endif
 #define LDPC_C3_POST_CHUNK_X 8   // posts of checks with >= this many info edges run new_v in stage-major chunks
 #endif
+#ifndef LDPC_C3_POST_STAGE7
+#define LDPC_C3_POST_STAGE7 1    // degree 7, fixed iterations: the post runs new_v of the 5 info edges and the x
+                                 // edge stage by stage (as the chunked post of degrees >= 10), then packs them
+                                 // two per v_perm (PACK2): r08 same box 32.14 -> 31.67 ms
+#endif
 template <int WS, int R, int SPW = 8>
 struct Cfg {
     static constexpr int S = SPW * WS;                 // checks per window
@@ -782,7 +787,44 @@ struct Slab3 {
                     put(ad, FZ ? perm(n, s.v[FZ_REREAD ? 0 : J], psel) : pack_v(n));   // FZ: pack_v of new / old per codeword
             };
             uint32_t nlast = 0;   // PACK2: the last info edge's new V, packed with the x edge's below
-            if constexpr (PACK2 && !FZ && !LEAN && (XL & 1)) {
+            uint32_t nxs = 0;     // ST7: the x edge's new V (staged with the info edges')
+            constexpr bool ST7 = LDPC_C3_POST_STAGE7 && PACK2 && !FZ && !LEAN && (XL & 1);
+            if constexpr (ST7) {
+                // new_v of the info edges and the x edge (slot XL here) stage by
+                // stage behind scheduling barriers, as the chunked post below:
+                // edge after edge each packed result waited a state for its one
+                // reader (an s_nop); stage-major the next edge's instruction fills it
+                constexpr int E = XL + 1;
+                uint32_t cv[E], av[E], nq[E], sc[E], T[E];
+#pragma unroll
+                for (int e = 0; e < XL; e++) cv[e] = s.c[e], av[e] = s.a[e];
+                cv[XL] = cx, av[XL] = ax;
+                static_for<0, E>([&](auto ec) __attribute__((always_inline)) {
+                    constexpr int e = decltype(ec)::value;
+                    nq[e] = opaque(pk_sra15(pk_sub(min1, av[e])));   // -1: the edge gets cst2
+                    sc[e] = opaque(pk_sra15(cv[e]));                  // -1: c < 0
+                });
+                __builtin_amdgcn_sched_barrier(0);
+                static_for<0, E>([&](auto ec) __attribute__((always_inline)) {
+                    constexpr int e = decltype(ec)::value;
+                    T[e] = pk_add_sat(av[e], bfi(nq[e], e2, e1));   // R(|c| + eps cst), capped at R(127)
+                });
+                __builtin_amdgcn_sched_barrier(0);
+                static_for<0, E>([&](auto ec) __attribute__((always_inline)) {
+                    constexpr int e = decltype(ec)::value, J = e < XL ? e : SX;
+                    MA[J >> 3] = add_code<J & 7>(MA[J >> 3], sc[e], nq[e]);
+                    T[e] = bfi(sc[e], pk_sub(K.c510, T[e]), T[e]);   // new_v's result
+                });
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int j = 0; j + 1 < XL; j += 2) {
+                    const uint32_t w = perm(T[j + 1], T[j], 0x07050301u);   // pack_v(T[j]) | pack_v(T[j + 1]) << 16
+                    put(ad_of(g, s, j), w);
+                    put(ad_of(g, s, j + 1), w >> 16);
+                }
+                nlast = T[XL - 1];
+                nxs = T[XL];
+            } else if constexpr (PACK2 && !FZ && !LEAN && (XL & 1)) {
                 uint32_t n[XL];
                 static_for<0, XL>([&](auto jc) __attribute__((always_inline)) {
                     constexpr int J = decltype(jc)::value;
@@ -840,7 +882,8 @@ struct Slab3 {
             }
             if constexpr (MP >= 0) __builtin_amdgcn_s_setprio(MP);   // mid-phase wave priority (fast periods)
             // x edge: for converged codewords the chain passed V[p_{i-1}] unchanged
-            const uint32_t nx = nv(std::integral_constant<int, SX>{}, cx, ax, min1, e1, e2);
+            uint32_t nx = nxs;
+            if constexpr (!ST7) nx = nv(std::integral_constant<int, SX>{}, cx, ax, min1, e1, e2);
             if constexpr (PACK2 && !FZ && !LEAN && (XL & 1)) {
                 const uint32_t w = perm(nx, nlast, 0x07050301u);
                 put(ad_of(g, s, XL - 1), w);
@@ -927,6 +970,14 @@ struct Slab3 {
 // PF2: the constants read two blocks of 8 steps ahead instead of one (degree
 // 10 only: r2/3 36.38 -> 35.79 ms same box; r1/2 +0.6 %, degrees 14 .. 30
 // within 0.5 %, r06ac / r06ad)
+// (One read per step boundary -- record i of the next block read right after
+// step i, pinned by scheduling barriers, two grouped waits per block instead
+// of one s_waitcnt per step: 227 instead of 250 instructions per r1/2 window,
+// 12 waits instead of 39 -- ran SLOWER, r08 same box: r1/2 32.14 -> 34.0 ms,
+// r2/3 35.9 -> 37.5, shaped r3/4 29.4 -> 30.9; stamps: 1806 -> 2083 cycles of
+// steps per r1/2 period.  The waits and s_nop cost the single chain wave
+// nothing it was not waiting for anyway; an LDS read between two dependent
+// steps does.  The burst at the block top stays.)
 template <int WS, int R, int B0, int B1, bool NMS = false, bool PF2 = false, typename SMT>
 LDPC_DEV void chain_window3(SMT &sm, int buf, int c, uint32_t (&w)[4])
 {

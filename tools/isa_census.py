@@ -74,11 +74,64 @@ def coop3_slab_paths(L, mn):
     return out
 
 
+def _counts(mns):
+    c = collections.Counter(classify(m) for m in mns)
+    return dict(valu=c["valu"], salu=c["salu"] - sum(1 for m in mns if m == "s_waitcnt"), lds=c["lds"],
+                vmem=c["vmem"], waitcnt=sum(1 for m in mns if m == "s_waitcnt"), nop=c["nop"], all=len(mns))
+
+
+def coop3_memory_periods(L, mn):
+    """The memory wave's steady periods: the straight-line regions between two
+    period-closing vmcnt waits that hold its s_sleep (the prologue's gathers
+    sit between two such waits too, but sleep nowhere)."""
+    w = [i for i, l in enumerate(L) if "vmcnt(" in l and check_vmcnt.closes_period(L, i)]
+    out = []
+    for x, y in zip(w, w[1:]):
+        body = mn[x + 1:y]
+        if "s_sleep" not in body or any(m.startswith(("s_cbranch_scc", "s_cbranch_vcc", "s_branch")) for m in body):
+            continue
+        d = _counts(body)
+        d.update(lines=[x, y], valu_lane_ops_per_check_cw=round(d["valu"] * 64 / (48 * 16), 2))
+        out.append(d)
+    return out
+
+
+def coop3_chain_window(mn):
+    """The chain wave's window (fixed-iteration kernels hold one: every
+    v_pk_mad_i16 of the kernel is a chain step): from the branch that guards it
+    to the end of its last step, and per block of 8 steps (from its first step
+    to the next block's) the constant reads, how many of them directly follow
+    a step's last instruction (LDPC_C3_CHAIN_RD1 puts every one there), the
+    x-input writes, the waits and the s_nop."""
+    mad = [i for i, m in enumerate(mn) if m == "v_pk_mad_i16"]
+    if len(mad) < 16 or len(mad) % 8:
+        return None
+    b = mad[0]
+    while not mn[b].startswith(("s_cbranch", "s_branch", "s_barrier")):
+        b -= 1
+    e = mad[-1]
+    while mn[e] != "v_med3_i16" or mn[e + 1] == "v_med3_i16":
+        e += 1   # the step's last v_med3_i16
+    out = _counts(mn[b + 1:e + 1])
+    out.update(lines=[b + 1, e + 1], steps=len(mad), blocks=[])
+    for k in range(0, len(mad), 8):
+        x, y = mad[k], mad[k + 8] if k + 8 < len(mad) else e + 1
+        rd = [i for i in range(x, y) if mn[i].startswith("ds_read")]
+        out["blocks"].append(dict(
+            reads=len(rd), reads_after_a_step=sum(1 for i in rd if mn[i - 1] == "v_med3_i16" and mn[i - 2] == "v_med3_i16"),
+            writes=sum(1 for i in range(x, y) if mn[i].startswith("ds_write")),
+            valu=sum(1 for i in range(x, y) if mn[i].startswith("v_")),
+            waitcnt=sum(1 for i in range(x, y) if mn[i] == "s_waitcnt"),
+            nop=sum(1 for i in range(x, y) if mn[i] == "s_nop")))
+    return out
+
+
 def coop3_census(funcs, kernel="coop3_decodeILi7ELi6ELi2ELb0ELb0ELb0E"):
     """One steady period of coop3 (DVB-S2 r1/2, WS = 6): the slab waves' fast
     period split at its branches (the shared prefix, the post variants for
-    slab wave 0 / the others, the pre), a memory-wave period (between two
-    period-closing vmcnt waits) and a chain block of 8 steps; VALU also as lane-ops per
+    slab wave 0 / the others, the pre), the memory wave's unrolled steady
+    periods (coop3_memory_periods), a chain block of 8 steps and the chain
+    window with its blocks (coop3_chain_window); VALU also as lane-ops per
     check x codeword (a slab lane = one check x 2 codewords; the memory and
     chain waves serve a window's 48 checks x 16 codewords); and the two slab
     paths of each unrolled steady period (coop3_slab_paths)."""
@@ -100,19 +153,13 @@ def coop3_census(funcs, kernel="coop3_decodeILi7ELi6ELi2ELb0ELb0ELb0E"):
         c = collections.Counter(classify(m) for m in mn[x + 1:y])
         parts.append(dict(lines=[x, y], valu=c["valu"], salu=c["salu"], lds=c["lds"], nop=c["nop"]))
     out["slab_fast_period_blocks"] = parts
-    w = [i for i, l in enumerate(L) if "vmcnt(" in l and check_vmcnt.closes_period(L, i)]
-    for x, y in zip(w, w[1:]):
-        if not any(mn[i].startswith(("s_cbranch_scc", "s_cbranch_vcc", "s_branch")) for i in range(x + 1, y)):
-            c = collections.Counter(classify(m) for m in mn[x + 1:y])
-            out["memory_wave_period"] = dict(lines=[x, y], valu=c["valu"], salu=c["salu"], lds=c["lds"],
-                                             vmem=c["vmem"], nop=c["nop"],
-                                             valu_lane_ops_per_check_cw=round(c["valu"] * 64 / (48 * 16), 2))
-            break
+    out["memory_wave_periods"] = coop3_memory_periods(L, mn)
     mad = [i for i, m in enumerate(mn) if m == "v_pk_mad_i16"]
     if len(mad) >= 16:
         x, y = mad[8], mad[16]
         c = collections.Counter(classify(m) for m in mn[x:y])
         out["chain_8_steps"] = dict(valu=c["valu"], lds=c["lds"], salu=c["salu"])
+    out["chain_window"] = coop3_chain_window(mn)
     return out
 
 
