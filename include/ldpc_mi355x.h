@@ -90,11 +90,16 @@ enum {
                               must be the true LLR 2y / sigma^2.  Int8 input: LDPC_EUNSUPPORTED
                               (the reference has no fixed-point BP).  Runs on LDPC_KERNEL_LDS
                               (the automatic choice where lds_f32 of ldpc_code_layer_info
-                              prefers it) and LDPC_KERNEL_GENERIC (any code); every other
-                              forced family is LDPC_EUNSUPPORTED.  The fast float families
-                              LDPC_KERNEL_LDSEP and LDPC_KERNEL_STAIRF have no BP yet, so a
-                              DVB-S2 code decodes BP on the generic kernel: correct, slow;
-                              ldpc_ctx_last_skipped names the family passed over */
+                              prefers it), LDPC_KERNEL_GENERIC (any code) and, on a context
+                              with ldpc_ctx_set_bp_staircase on, LDPC_KERNEL_STAIRF (the
+                              DVB-S2 staircase codes, bit for bit the same results); every
+                              other forced family is LDPC_EUNSUPPORTED.  With that switch off
+                              (the default) a DVB-S2 code decodes BP on the generic kernel:
+                              correct, slow; ldpc_ctx_last_skipped then names
+                              LDPC_KERNEL_STAIRF as the family passed over.
+                              LDPC_KERNEL_LDSEP has no BP: its parallel prefix over the
+                              edges would reorder the box-plus chain, and LDPC_KERNEL_LDS
+                              serves those codes */
 };
 
 typedef struct ldpc_code ldpc_code;
@@ -208,7 +213,8 @@ typedef enum ldpc_kernel {
     LDPC_KERNEL_STAIRF = 11     /* float, DVB-S2 staircase codes: S consecutive checks of 64/S codewords
                                    per wave, the staircase chain by DPP; the automatic choice for float
                                    decodes of those codes, early termination by one launch per
-                                   iteration + a syndrome pass */
+                                   iteration + a syndrome pass.  Min-sum (OMS / NMS / MS) always;
+                                   LDPC_ALGO_BP after ldpc_ctx_set_bp_staircase(ctx, 1) */
 } ldpc_kernel;
 /* Select the kernel family (an ldpc_kernel value): LDPC_KERNEL_AUTO .. LDPC_KERNEL_LDSEP
  * or LDPC_KERNEL_STAIRF.  A value outside 0 .. 11, or LDPC_KERNEL_HOST, is
@@ -216,6 +222,31 @@ typedef enum ldpc_kernel {
  * 4 and 6 included) is LDPC_EUNSUPPORTED and leaves the selection as it was. */
 int ldpc_ctx_set_kernel(ldpc_ctx *ctx, int kernel);
 int ldpc_ctx_get_kernel(ldpc_ctx *ctx, int *kernel);
+/* Belief propagation on the staircase kernel (off by default).  On: an
+ * LDPC_ALGO_BP decode of a float staircase code runs on LDPC_KERNEL_STAIRF --
+ * the automatic choice wherever that family takes the batch (last_skipped 0),
+ * and what a forced LDPC_KERNEL_STAIRF runs.  A batch too large for the family
+ * ((n + 1) * stride * 4 >= 2^32, stride = the batch rounded up to 64) decodes
+ * on LDPC_KERNEL_GENERIC under the automatic choice, and last_skipped names
+ * LDPC_KERNEL_STAIRF (with the switch off it stays 0 for such a batch, as
+ * before); forced LDPC_KERNEL_STAIRF is then LDPC_EUNSUPPORTED.  Forced LDPC_KERNEL_GENERIC / LDPC_KERNEL_LDS and
+ * every other algorithm are unchanged.  Results equal the host decoder's bit
+ * for bit on either kernel.  Off: BP never runs on LDPC_KERNEL_STAIRF (forced:
+ * LDPC_EUNSUPPORTED).  set: LDPC_EUNSUPPORTED on a host context or a code
+ * without a staircase table (ldpc_ctx_set_kernel(ctx, LDPC_KERNEL_STAIRF) fails
+ * on the same codes), the setting stays as it was; LDPC_EINVAL for a NULL ctx. */
+int ldpc_ctx_set_bp_staircase(ldpc_ctx *ctx, int enable);
+int ldpc_ctx_get_bp_staircase(ldpc_ctx *ctx, int *enable);
+/* The group width S (checks per wave group: 2, 4, 8 or 16) that a BP decode on
+ * LDPC_KERNEL_STAIRF picks when LDPC_STAIRF_S does not force one: x information
+ * edges per check, m checks, stride = the batch rounded up to 64, widths = the
+ * widths the code has a table for (bit S set).  The least modelled cost
+ * (m / S) * (3x - 1 + S) * f(w), w = stride * S / 64 / 256 waves per CU,
+ * f = 1 up to two waves and (w / 2)^(5/8) beyond (fitted to measurement,
+ * DESIGN.md section 7), the wider on a tie; 0 when no width in the mask divides m.
+ * (Introspection for tests; needs no context and no GPU.  Unstable: the model
+ * is fitted to one code and may change, or the entry go, in any release.) */
+int ldpc_bp_staircase_width_model(int x, int m, int stride, unsigned widths);
 /* Kernel family the last decode actually ran (an ldpc_kernel value;
  * LDPC_KERNEL_HOST on a device -1 context, 0 before the first decode). */
 int ldpc_ctx_last_kernel(ldpc_ctx *ctx, int *kernel);

@@ -85,6 +85,14 @@ public:
         check(ldpc_decode_f32(ctx_, var_nodes, reinterpret_cast<uint8_t *>(Rprime_fix), frames_, nombre_iterations,
                               &fp));
     }
+    // LDPC_ALGO_BP on the staircase kernel of the DVB-S2 codes (ldpc_ctx_set_bp_staircase; off by default)
+    void setBpStaircase(bool on) { check(ldpc_ctx_set_bp_staircase(ctx_, on ? 1 : 0)); }
+    bool bpStaircase()
+    {
+        int on = 0;
+        check(ldpc_ctx_get_bp_staircase(ctx_, &on));
+        return on != 0;
+    }
     ldpc_ctx *context() { return ctx_; }
 
 protected:

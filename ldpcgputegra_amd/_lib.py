@@ -85,6 +85,9 @@ SIGNATURES = {
     "ldpc_ctx_stream": (I, [P, C.POINTER(P)]),
     "ldpc_ctx_set_kernel": (I, [P, I]),
     "ldpc_ctx_get_kernel": (I, [P, C.POINTER(I)]),
+    "ldpc_ctx_set_bp_staircase": (I, [P, I]),
+    "ldpc_ctx_get_bp_staircase": (I, [P, C.POINTER(I)]),
+    "ldpc_bp_staircase_width_model": (I, [I, I, I, C.c_uint]),
     "ldpc_ctx_last_kernel": (I, [P, C.POINTER(I)]),
     "ldpc_ctx_last_skipped": (I, [P, C.POINTER(I)]),
     "ldpc_ctx_last_et_stage": (I, [P, C.POINTER(I)]),

@@ -154,6 +154,23 @@ extern "C" int ldpc_ctx_set_kernel(ldpc_ctx *c, int k)
     return LDPC_OK;
 }
 
+extern "C" int ldpc_ctx_set_bp_staircase(ldpc_ctx *c, int enable)
+{
+    if (!c) return ldpc_set_error(LDPC_EINVAL, "NULL ctx");
+    if (c->device < 0 || !c->stairf.valid)
+        return ldpc_set_error(LDPC_EUNSUPPORTED, "belief propagation on the staircase kernel: %s",
+                              c->device < 0 ? "host context" : "the code has no staircase table");
+    c->bp_staircase = enable != 0;
+    return LDPC_OK;
+}
+
+extern "C" int ldpc_ctx_get_bp_staircase(ldpc_ctx *c, int *enable)
+{
+    if (!c || !enable) return ldpc_set_error(LDPC_EINVAL, "NULL");
+    *enable = c->bp_staircase ? 1 : 0;
+    return LDPC_OK;
+}
+
 extern "C" int ldpc_ctx_profile(ldpc_ctx *c, int enable)
 {
     if (!c) return ldpc_set_error(LDPC_EINVAL, "NULL ctx");

@@ -62,6 +62,7 @@ struct ldpc_ctx {
     int last_lds_lanes = 0;         // LDPC_KERNEL_LDS's last launch: lanes per codeword, two lanes per check or not
     int last_lds_split = 0;         // (0 / 0 when the last decode was not on that kernel)
     int last_skipped = 0;   // the preferred kernel the last decode could not use at its batch size (0: none)
+    bool bp_staircase = false;   // LDPC_ALGO_BP may run on the staircase kernel (ldpc_ctx_set_bp_staircase)
     int lds_pad = 0;        // extra dynamic LDS per windowed2 workgroup (ldpc_ctx_set_lds_pad)
     hipStream_t stream = nullptr;
     // device copy of the code

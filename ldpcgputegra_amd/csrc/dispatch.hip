@@ -64,14 +64,18 @@ static int pick_kernel(ldpc_ctx *c, const ldpc_params *p, bool is_float, int str
     const ldpc_code *h = c->code;
     const bool automatic = c->kernel == LDPC_KERNEL_AUTO;
     const bool sf = family_fits(c, LDPC_KERNEL_STAIRF) && stairf_stride_ok(c->stairf, h->n, stride);
-    if (p->algo == LDPC_ALGO_BP) {   // float only (check_params); bp.hip has the LDS-resident and the any-H kernel
+    if (p->algo == LDPC_ALGO_BP) {   // float only (check_params); bp.hip has the LDS-resident and the any-H kernel,
+                                     // stairbp.hip the staircase one behind ldpc_ctx_set_bp_staircase
         if (c->kernel == LDPC_KERNEL_LDS) return lds_applicable(h, c->lds, true) ? LDPC_KERNEL_LDS : -1;
         if (c->kernel == LDPC_KERNEL_GENERIC) return LDPC_KERNEL_GENERIC;
+        if (c->kernel == LDPC_KERNEL_STAIRF) return (c->bp_staircase && sf) ? LDPC_KERNEL_STAIRF : -1;
         if (!automatic) return -1;
         if (ldsep_applicable(h, c->lds, true))
             c->last_skipped = LDPC_KERNEL_LDSEP;
-        else if (sf)
-            c->last_skipped = LDPC_KERNEL_STAIRF;
+        else if (sf && c->bp_staircase)
+            return LDPC_KERNEL_STAIRF;
+        else if (sf || (c->bp_staircase && family_fits(c, LDPC_KERNEL_STAIRF)))
+            c->last_skipped = LDPC_KERNEL_STAIRF;   // no BP there (switch off), or on and the stride too large
         return lds_preferred(h, c->lds, true) ? LDPC_KERNEL_LDS : LDPC_KERNEL_GENERIC;
     }
     switch (c->kernel) {
@@ -365,7 +369,8 @@ static int decode_in_scratch(ldpc_ctx *c, Scratch &sc, hipStream_t s, int kern, 
         switch (kern) {
         case LDPC_KERNEL_COOP3: return launch_coop3(L, c->coop3, s);
         case LDPC_KERNEL_COOP: return launch_coop(L, c->coop, s);
-        case LDPC_KERNEL_STAIRF: return launch_stairf(L, c->stairf, s);
+        case LDPC_KERNEL_STAIRF:
+            return L.algo == LDPC_ALGO_BP ? launch_stairbp(L, c->stairf, s) : launch_stairf(L, c->stairf, s);
         case LDPC_KERNEL_WINDOWED2: return launch_windowed2(L, c->w16, s);
         case LDPC_KERNEL_WINDOWED: return launch_windowed(L, c->wcode, s);
         default: return L.algo == LDPC_ALGO_BP ? launch_bp_generic(L, s) : launch_generic(L, s);

@@ -11,7 +11,7 @@
 //   ldpc_sim -code dvbs2_r1_2 -min 0.8 -max 1.2 -pas 0.1 -iter 50 -fer 100
 //            [-batch 4096] [-frames 1000000] [-OMS 1 | -NMS 29 | -MS]
 //            [-encoder [-fresh] | -gencoder [-fresh]] [-et] [-gpus N] [-seed S]
-//            [-kernel K] [-f32 [-beta B] | -f32q | -BP]
+//            [-kernel K] [-f32 [-beta B] | -f32q | -BP [-bpstair]]
 //
 // Three chains see the same noise (one u per element, the same first_cw and
 // seed scheme): the default draws the quantised int8 LLRs directly
@@ -26,6 +26,9 @@
 // yardstick curve of the three min-sum algorithms.  BP is not scale-invariant,
 // so its channel is drawn with norm = 2 / sigma^2 (true LLRs) where the other
 // -f32 runs keep 1.0; there is no int8 BP, so -BP with -f32q is a usage error.
+// -bpstair (with -BP only) lets BP run on the staircase kernel of the DVB-S2
+// codes (ldpc_ctx_set_bp_staircase): the same counts, many times the frames per
+// second; the JSON line names it ("bp_staircase").
 //
 // -encoder alone draws 64 codewords once on the host and replicates them over
 // every batch; -encoder -fresh draws new information bits and encodes them on
@@ -58,7 +61,7 @@ struct Opt {
     double min = 0.5, max = 3.0, pas = 0.1;
     int iter = 30, fer = 100, batch = 4096, gpus = 1, kernel = LDPC_KERNEL_AUTO;
     long frames = 1 << 20;
-    bool encoder = false, gencoder = false, fresh = false, f32 = false, f32q = false, bp = false;
+    bool encoder = false, gencoder = false, fresh = false, f32 = false, f32q = false, bp = false, bpstair = false;
     ldpc_params p{};
     uint64_t seed = 1;
 };
@@ -98,6 +101,7 @@ void worker(int dev, const ldpc_code *h, const Opt &o, double sigma, Totals &tot
     CHECK(ldpc_ctx_create(h, dev, o.batch, &ctx));
     if (genc && o.fresh) CHECK(ldpc_ctx_set_encoder(ctx, genc));
     if (o.kernel) CHECK(ldpc_ctx_set_kernel(ctx, o.kernel));
+    if (o.bpstair) CHECK(ldpc_ctx_set_bp_staircase(ctx, 1));
     void *stream;
     CHECK(ldpc_ctx_stream(ctx, &stream));
     uint32_t table[64];
@@ -195,6 +199,7 @@ int main(int argc, char **argv)
         else if (a == "-NMS") { o.p.algo = LDPC_ALGO_NMS; o.p.factor = atoi(nxt()); }
         else if (a == "-MS") o.p.algo = LDPC_ALGO_MS;
         else if (a == "-BP") o.bp = true;
+        else if (a == "-bpstair") o.bpstair = true;
         else if (a == "-encoder") o.encoder = true;
         else if (a == "-gencoder") o.gencoder = true;
         else if (a == "-fresh") o.fresh = true;
@@ -225,6 +230,10 @@ int main(int argc, char **argv)
         }
         o.f32 = true;
         o.p.algo = LDPC_ALGO_BP;
+    }
+    if (o.bpstair && !o.bp) {
+        fprintf(stderr, "usage: -bpstair (belief propagation on the staircase kernel) needs -BP\n");
+        return 2;
     }
     if (o.fresh && !o.encoder && !o.gencoder) {
         fprintf(stderr, "usage: -fresh (new codewords every frame) needs -encoder\n");
@@ -280,8 +289,8 @@ int main(int argc, char **argv)
                "BE/FE = %.1f | RUNTIME = %.2fs\n",
                eb, ber, fer, (double)fr * k / sec / 1e6, fr, fe, be, fe ? (double)be / fe : 0.0, sec);
         printf("{\"ebn0\": %.3f, \"sigma\": %.6f, \"frames\": %ld, \"frame_errors\": %ld, \"bit_errors\": %ld, "
-               "\"ber\": %.6e, \"fer\": %.6e, \"coded_mbps\": %.3f, \"chain\": \"%s\", \"algo\": \"%s\"}\n",
-               eb, sigma, fr, fe, be, ber, fer, mbps, chain, algo);
+               "\"ber\": %.6e, \"fer\": %.6e, \"coded_mbps\": %.3f, \"chain\": \"%s\", \"algo\": \"%s\", \"bp_staircase\": %s}\n",
+               eb, sigma, fr, fe, be, ber, fer, mbps, chain, algo, o.bpstair ? "true" : "false");
         fflush(stdout);
     }
     ldpc_encoder_destroy(genc);

@@ -25,3 +25,10 @@ bool stairf_stride_ok(const StairfCode &sc, int n, int stride);
 // message scratch of one decode (the kernel's own layout, zeroed by the caller)
 size_t stairf_msg_bytes(const StairfCode &sc, int stride);
 int launch_stairf(const DecodeLaunch &L, const StairfCode &sc, hipStream_t s);
+// group width S of a launch at this stride (0: the code has no table); bp: the
+// rule of the belief-propagation kernel (stairbp.hip) instead of min-sum's
+int stairf_width(const StairfCode &sc, int stride, bool bp = false);
+// the BP rule alone: least modelled cost over the widths in the mask (bit S set)
+int stairbp_model_width(int X, int m, int stride, unsigned widths);
+// belief propagation (LDPC_ALGO_BP) on the same tables, V and message layout (stairbp.hip)
+int launch_stairbp(const DecodeLaunch &L, const StairfCode &sc, hipStream_t s);

@@ -37,28 +37,11 @@
 #include <cstdlib>
 #include <vector>
 
-#include "stairf.h"
+#include "stairf_et.h"
 
 namespace {
 
-struct StairfArgs {
-    float *V;
-    float *msg;
-    const uint32_t *tab;
-    int G, T, stride, iters, x0;
-    float beta;
-    const uint8_t *live;   // early termination: codewords still decoding (stores of the others are off)
-};
-
-template <int X, int S>
-struct SF {
-    static constexpr int W = (X + 3) / 2;   // u32 words of packed u16 node ids per check
-    static constexpr int E = X + 2;         // messages per check
-    // groups in flight: ring registers 2P * W + P * (2X + 3) stay <= ~180, and
-    // S * P <= 48 checks (every DVB-S2 code's hazard distance is >= 51)
-    static constexpr int PR = X <= 5 ? 8 : X <= 8 ? 6 : X <= 12 ? 4 : 2;
-    static constexpr int P = PR < 48 / S ? PR : 48 / S;
-};
+using namespace stairf_dev;
 
 constexpr bool x_supported(int X) { return X == 5 || X == 8 || X == 12 || X == 20 || X == 25 || X == 28; }
 
@@ -77,7 +60,6 @@ int p_of(int X)
 }
 
 int p_of_s(int X, int S) { return S == 2 ? p_of<2>(X) : S == 4 ? p_of<4>(X) : S == 8 ? p_of<8>(X) : p_of<16>(X); }
-int s_index(int S) { return S == 2 ? 3 : S == 4 ? 0 : S == 8 ? 1 : 2; }
 
 // A: 0 OMS, 1 NMS, 2 OMS with beta = 0 (plain min-sum)
 template <int A>
@@ -91,19 +73,6 @@ LDPC_DEV float cst(float x, float beta)
         return x;
     else
         return fmaxf(x - beta, 0.0f);
-}
-
-// chain step `step`: slot `step` reads slot step - 1 of its codeword (row_shr:1),
-// slot 0 reads slot S - 1 (row_shl:S-1; the previous group's last check)
-template <int S>
-LDPC_DEV float rot_chain(float t, int step)
-{
-    // bound_ctrl: lanes whose source is outside the row read 0 (none of them is
-    // the step's valid slot), which lets the move fold into the subtract that
-    // consumes it (v_sub_f32_dpp): one dependent instruction less per step
-    const int v = __float_as_int(t);
-    return __int_as_float(step == 0 ? __builtin_amdgcn_update_dpp(0, v, 0x100 + S - 1, 0xF, 0xF, true)
-                                    : __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, true));
 }
 
 template <int X, int A, int S, bool ET>
@@ -244,60 +213,6 @@ int launch_xs(const StairfArgs &a, int blocks, int algo, hipStream_t s)
     return a.live ? launch_xse<X, S, true>(a, blocks, algo, s) : launch_xse<X, S, false>(a, blocks, algo, s);
 }
 
-// early termination (oracle_decode_f32: stop a codeword after the first
-// iteration whose hard decisions V > 0 satisfy every check): after each
-// one-iteration launch, every check of every live codeword is tested (one
-// lane per codeword, a chunk of checks per workgroup, the check's nodes
-// wave-uniform), any failing check marks the codeword bad; then live
-// codewords without a bad mark stop with that iteration count
-__global__ void __launch_bounds__(64) stairf_et_init_k(uint8_t *live, uint32_t *bad, int32_t *iters_used, int batch,
-                                                       int stride, int iters)
-{
-    const int b = blockIdx.x * 64 + threadIdx.x;
-    if (b >= stride) return;
-    live[b] = b < batch;
-    bad[b] = 0;
-    if (b < batch) iters_used[b] = iters;
-}
-
-// without early termination every codeword runs all the iterations
-__global__ void __launch_bounds__(64) stairf_fill_iters_k(int32_t *iters_used, int batch, int iters)
-{
-    const int b = blockIdx.x * 64 + threadIdx.x;
-    if (b < batch) iters_used[b] = iters;
-}
-
-__global__ void __launch_bounds__(64) stairf_syndrome_k(const float *V, const uint32_t *ev, const uint8_t *live,
-                                                        uint32_t *bad, int m, int d0, int chunk, int stride)
-{
-    const int b = blockIdx.x * 64 + threadIdx.x;
-    const bool on = live[b] != 0;
-    if (!__any(on)) return;
-    const int c0 = blockIdx.y * chunk, c1 = min(m, c0 + chunk);
-    const float *Vb = V + b;
-    int fail = 0;
-    for (int c = c0; c < c1; c++) {
-        const uint32_t *e = ev + (size_t)c * d0;   // layered order: every check d0 edges apart, the tail last
-        const int d = c == m - 1 ? d0 - 1 : d0;
-        int par = 0;
-        for (int j = 0; j < d; j++) par ^= Vb[(size_t)e[j] * stride] > 0.0f;
-        fail |= par;
-    }
-    if (on && fail) bad[b] = 1;
-}
-
-__global__ void __launch_bounds__(64) stairf_et_step_k(uint8_t *live, uint32_t *bad, int32_t *iters_used, int batch,
-                                                       int it)
-{
-    const int b = blockIdx.x * 64 + threadIdx.x;
-    if (b >= batch) return;
-    if (live[b] && !bad[b]) {
-        live[b] = 0;
-        iters_used[b] = it;
-    }
-    bad[b] = 0;
-}
-
 template <int X>
 int launch_x(const StairfArgs &a, int S, int blocks, int algo, hipStream_t s)
 {
@@ -366,10 +281,16 @@ int stairf_upload(const ldpc_code *h, StairfCode *sc)
 //   batch  2048: 132.8 / 74.9 / 53.7 / 67.1
 //   batch  4096: 137.5 / 80.1 / 117.8 / 179.9
 //   batch 16384: 234.3 / 356.1 / 507.2 / 830.3 (S = 2: 4.73 TB/s of HBM traffic)
-int stairf_width(const StairfCode &sc, int stride)
+// Belief propagation (bp) is VALU-bound instead: stairbp_model_width (stairbp.hip).
+int stairf_width(const StairfCode &sc, int stride, bool bp)
 {
     const char *e = getenv("LDPC_STAIRF_S");
-    const int want = (e && *e) ? atoi(e) : stride >= 8192 ? 2 : stride >= 4096 ? 4 : stride >= 2048 ? 8 : 16;
+    unsigned have = 0;
+    for (int S : {2, 4, 8, 16})
+        if (sc.d_tab[s_index(S)]) have |= (unsigned)S;
+    const int want = (e && *e) ? atoi(e)
+                     : bp      ? stairbp_model_width(sc.X, sc.m, stride, have)
+                     : stride >= 8192 ? 2 : stride >= 4096 ? 4 : stride >= 2048 ? 8 : 16;
     // (2 last: a code whose min_hazard leaves only the narrowest table is valid, so some width must be found)
     for (int S : {want, 8, 4, 16, 2})
         if ((S == 2 || S == 4 || S == 8 || S == 16) && sc.d_tab[s_index(S)]) return S;
@@ -399,20 +320,10 @@ int launch_stairf(const DecodeLaunch &L, const StairfCode &sc, hipStream_t s)
     if (L.early && (!L.live || !L.bad || !L.iters_used || !L.d_edge_var)) return -1;
     const int S = stairf_width(sc, L.stride);
     if (!S) return -1;
-    StairfArgs a;
-    a.V = (float *)L.V;
-    a.msg = (float *)L.msg;
-    a.tab = sc.d_tab[s_index(S)];
-    a.G = sc.m / S;
-    a.T = sc.m - 1;
-    a.stride = L.stride;
-    a.iters = L.iters;
-    a.x0 = sc.x0;
-    a.beta = L.beta;
-    a.live = nullptr;
+    const StairfArgs a0 = make_args(L, sc, S);
     const int algo = L.algo == 1 ? 1 : L.beta == 0.0f ? 2 : 0;
     const int blocks = L.stride / (64 / S);
-    auto run = [&]() {
+    auto run = [&](const StairfArgs &a) {
         switch (sc.X) {
         case 5: return launch_x<5>(a, S, blocks, algo, s);
         case 8: return launch_x<8>(a, S, blocks, algo, s);
@@ -423,28 +334,5 @@ int launch_stairf(const DecodeLaunch &L, const StairfCode &sc, hipStream_t s)
         }
         return -1;
     };
-    if (!L.early) {
-        if (L.iters_used) {   // as the other kernels report it (generic.hip, coop3.hip fill_iters3_k)
-            hipLaunchKernelGGL(stairf_fill_iters_k, dim3((L.batch + 63) / 64), dim3(64), 0, s, L.iters_used, L.batch,
-                               L.iters);
-            if (hipGetLastError() != hipSuccess) return -1;
-        }
-        return L.iters <= 0 ? 0 : run();
-    }
-    // early termination: one launch per iteration, then the syndrome
-    const int cb = L.stride / 64;
-    hipLaunchKernelGGL(stairf_et_init_k, dim3(cb), dim3(64), 0, s, L.live, L.bad, L.iters_used, L.batch, L.stride,
-                       L.iters);
-    if (hipGetLastError() != hipSuccess) return -1;
-    const int chunks = std::max(1, std::min(sc.m, 4096 / cb)), chunk = (sc.m + chunks - 1) / chunks;
-    a.iters = 1;
-    a.live = L.live;
-    for (int it = 1; it <= L.iters; it++) {
-        if (run()) return -1;
-        hipLaunchKernelGGL(stairf_syndrome_k, dim3(cb, (sc.m + chunk - 1) / chunk), dim3(64), 0, s, (const float *)L.V,
-                           L.d_edge_var, L.live, L.bad, sc.m, sc.X + 2, chunk, L.stride);
-        hipLaunchKernelGGL(stairf_et_step_k, dim3(cb), dim3(64), 0, s, L.live, L.bad, L.iters_used, L.batch, it);
-        if (hipGetLastError() != hipSuccess) return -1;
-    }
-    return 0;
+    return run_decode(L, sc, a0, s, run);
 }

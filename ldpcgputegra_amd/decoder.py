@@ -54,7 +54,7 @@ def boxplus_host(a, b):
 class Decoder:
     """One C-ABI decoder context (device scratch for ``max_batch`` codewords)."""
 
-    def __init__(self, code, device=0, max_batch=4096, kernel=0):
+    def __init__(self, code, device=0, max_batch=4096, kernel=0, bp_staircase=False):
         self.code = code if isinstance(code, Code) else Code(code)
         self.device = device
         self.max_batch = max_batch
@@ -64,6 +64,8 @@ class Decoder:
         self._pending = []   # (llr, hard) of queued host-buffer decodes, alive until synchronize()
         if kernel:
             self.set_kernel(kernel)
+        if bp_staircase:
+            self.set_bp_staircase(True)
 
     # -- configuration
     def set_kernel(self, kernel):
@@ -74,7 +76,8 @@ class Decoder:
         (edge-parallel float for short QC codes; the float default where it fits),
         11 = stairf (float staircase codes, DVB-S2: the float default for them,
         with or without early termination -- with it, one launch per iteration
-        plus a syndrome pass, as include/ldpc_mi355x.h states).  4 and 6 (windowed2 S = 32, coop2) were
+        plus a syndrome pass, as include/ldpc_mi355x.h states; ALGO_BP runs on it
+        after set_bp_staircase(True)).  4 and 6 (windowed2 S = 32, coop2) were
         superseded and removed."""
         _lib.check(_lib.lib().ldpc_ctx_set_kernel(self._ctx, int(kernel)))
 
@@ -83,6 +86,21 @@ class Decoder:
         k = C.c_int()
         _lib.check(_lib.lib().ldpc_ctx_get_kernel(self._ctx, C.byref(k)))
         return k.value
+
+    def set_bp_staircase(self, flag):
+        """Let ALGO_BP run on stairf (11), the staircase kernel of the DVB-S2
+        codes: then the automatic choice for BP wherever stairf takes the batch,
+        and what a forced kernel 11 runs.  Off (the default) BP decodes those
+        codes on generic.  Bit for bit the same results either way.  Raises
+        LDPC_EUNSUPPORTED on a host decoder or a code without a stairf table
+        (``ldpc_ctx_set_bp_staircase``)."""
+        _lib.check(_lib.lib().ldpc_ctx_set_bp_staircase(self._ctx, int(bool(flag))))
+
+    @property
+    def bp_staircase(self):
+        on = C.c_int()
+        _lib.check(_lib.lib().ldpc_ctx_get_bp_staircase(self._ctx, C.byref(on)))
+        return bool(on.value)
 
     def profile(self, enable=True):
         """Record HIP events around every decode kernel launch."""
