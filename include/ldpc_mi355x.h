@@ -325,7 +325,8 @@ void ldpc_host_free(void *ptr);
  * Buffer contract of every device-pointer entry point (decode, mixed decode,
  * channel, quantiser, bit source, encoders, error count):
  *  - a device buffer needs only the natural alignment of its element type:
- *    1 byte for int8 / uint8, 4 for float / int32, 8 for the error counters.
+ *    1 byte for int8 / uint8, 2 for binary16, 4 for float / int32, 8 for the
+ *    error counters.
  *    A contiguous slice of a larger allocation is a valid argument; wider
  *    alignment (16 bytes) only selects faster load / store paths, never
  *    another result;
@@ -363,6 +364,56 @@ int ldpc_decode_i8_nm_async(ldpc_ctx *ctx, void *hip_stream, const int8_t *d_llr
 int ldpc_boxplus_f32_host(const float *a, const float *b, float *out, long count);
 int ldpc_boxplus_f32_async(ldpc_ctx *ctx, void *hip_stream, const float *d_a, const float *d_b, float *d_out,
                            long count);
+
+/* ---- binary16 ("f16") decode --------------------------------------------- */
+/* Layered min-sum in IEEE binary16, between the int8 and the float32 decode:
+ * half the bytes of float32 per LLR, per V and per message.  binary16 values
+ * travel as uint16_t bit patterns.  The half contract defines
+ * the results bit for bit: every + - x rounded to nearest even to binary16,
+ * min / max / abs exact, subnormals kept; V saturates at +-1024 (on load and
+ * after every update, +-inf included), the messages a check sends at 256; the
+ * sign of a contribution is its sign bit (-0.0 counts as negative); the hard
+ * decision V > 0 is a comparison (+-0 give 0).  NaN input is outside the
+ * contract.  Parameters: algo OMS / NMS / MS with beta (rounded to binary16)
+ * and early_term; LDPC_ALGO_BP is LDPC_EUNSUPPORTED; a beta that is negative,
+ * not finite or rounds to binary16 infinity is LDPC_EINVAL (MS ignores beta);
+ * the int8 fields are ignored.
+ *
+ * ldpc_decode_f16_async: device buffers, the conventions and buffer contract
+ * of ldpc_decode_f32_async with 2-byte element alignment; rows beyond `batch`
+ * are never written although the kernel packs codewords in pairs.  On the GPU
+ * it decodes the staircase codes (every DVB-S2 table and the shaped ones) on
+ * the packed half-precision element type of LDPC_KERNEL_STAIRF, which
+ * ldpc_ctx_last_kernel then reports: two codewords per lane as one 32-bit
+ * pair.  Any other code is LDPC_EUNSUPPORTED on a GPU context, and so are a
+ * family other than AUTO / LDPC_KERNEL_STAIRF forced by ldpc_ctx_set_kernel
+ * and a batch beyond the kernel's 32-bit V offsets, (n + 1) * stride * 2 <
+ * 2^32 with stride = batch rounded up to 64 (33088 codewords at n = 64800,
+ * twice float32's limit).  LDPC_STAIRF_S forces the group width as for float32.
+ *
+ * ldpc_decode_f16: host buffers, synchronous: copy in, decode, copy out on a
+ * GPU context; the host decoder, which takes every code, on a device -1
+ * context (last_kernel LDPC_KERNEL_HOST).
+ * ldpc_decode_f16_soft: host context only, the twin of ldpc_decode_f32_soft:
+ * the definition the kernel is compared with. */
+int ldpc_decode_f16_async(ldpc_ctx *ctx, void *hip_stream, const uint16_t *d_llr, uint8_t *d_hard,
+                          uint16_t *d_soft, int32_t *d_iters_used, int batch, int n_iter,
+                          const ldpc_params *p);
+int ldpc_decode_f16(ldpc_ctx *ctx, const uint16_t *llr, uint8_t *hard, int batch, int n_iter,
+                    const ldpc_params *p);
+int ldpc_decode_f16_soft(ldpc_ctx *ctx, const uint16_t *llr, uint8_t *hard, uint16_t *soft, int32_t *iters_used,
+                         int batch, int n_iter, const ldpc_params *p);
+/* float32 -> binary16 LLRs: h = RNE16(min(max(y, -1024), 1024)).  _host needs
+ * no context; _async runs on the device of a GPU context (a host context is
+ * LDPC_EUNSUPPORTED), bit for bit the host's results.  count = 0 touches
+ * nothing; a NULL pointer with count > 0 or a negative count is LDPC_EINVAL. */
+int ldpc_convert_f32_f16_host(const float *y, uint16_t *h, long count);
+int ldpc_convert_f32_f16_async(ldpc_ctx *ctx, void *hip_stream, const float *d_y, uint16_t *d_h, long count);
+/* The group width S (2, 4, 8 or 16 checks of 128 / S codewords per wave) the
+ * binary16 kernel's rule picks at `stride` (the batch rounded up to 64) among
+ * `widths` (bit S set: the code has that table; 0: none).  Introspection for
+ * tools/f16_rate.py, which holds the rule against measured times. */
+int ldpc_f16_staircase_width_rule(int stride, unsigned widths);
 
 /* ---- mixed-rate batches (BASELINE config 5) ---------------------------- */
 /* A batch whose codewords use different codes of equal length N (e.g. the

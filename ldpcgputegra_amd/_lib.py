@@ -97,6 +97,12 @@ SIGNATURES = {
     "ldpc_decode_i8": (I, [P, P, P, I, I, C.POINTER(ldpc_params)]),
     "ldpc_decode_f32": (I, [P, P, P, I, I, C.POINTER(ldpc_params)]),
     "ldpc_decode_f32_soft": (I, [P, P, P, P, P, I, I, C.POINTER(ldpc_params)]),
+    "ldpc_decode_f16": (I, [P, P, P, I, I, C.POINTER(ldpc_params)]),
+    "ldpc_decode_f16_soft": (I, [P, P, P, P, P, I, I, C.POINTER(ldpc_params)]),
+    "ldpc_decode_f16_async": (I, [P, P, P, P, P, P, I, I, C.POINTER(ldpc_params)]),
+    "ldpc_convert_f32_f16_host": (I, [P, P, C.c_long]),
+    "ldpc_f16_staircase_width_rule": (I, [I, C.c_uint]),
+    "ldpc_convert_f32_f16_async": (I, [P, P, P, P, C.c_long]),
     "ldpc_boxplus_f32_host": (I, [P, P, P, C.c_long]),
     "ldpc_boxplus_f32_async": (I, [P, P, P, P, P, C.c_long]),
     "ldpc_decode_i8_async": (I, [P, P, P, P, P, P, I, I, C.POINTER(ldpc_params)]),

@@ -87,3 +87,13 @@ def awgn_f32_host(n, batch, seed, sigma, amp=BPSK, normalize=False, first_cw=0, 
     _lib.check(_lib.lib().ldpc_awgn_f32_host(n, batch, first_cw, seed, float(sigma), float(amp), float(norm), cw,
                                              out.ctypes.data))
     return out
+
+
+def convert_f16_host(y):
+    """float32 -> binary16 LLRs on the CPU (``ldpc_convert_f32_f16_host``,
+    bit-equal to ``Decoder.convert_f16_device``): clamp to +-1024, then round
+    to nearest even.  Returns a float16 array of y's shape."""
+    y = np.ascontiguousarray(y, dtype=np.float32)
+    h = np.empty(y.shape, dtype=np.float16)
+    _lib.check(_lib.lib().ldpc_convert_f32_f16_host(y.ctypes.data, h.ctypes.data, y.size))
+    return h

@@ -206,6 +206,97 @@ int decode_one_f32(const ldpc_code *h, const float *llr, uint8_t *hard, int iter
     return it;
 }
 
+// ---- binary16: the half contract.  Values travel as bit
+// patterns; every + - x is computed in float and rounded once to binary16
+// (round to nearest even), which gives the bits of an IEEE binary16 operation.
+typedef _Float16 f16;
+constexpr uint16_t H_INF = 0x7C00, H_VSAT = 0x6400, H_MSAT = 0x5C00;   // +inf, 1024, 256
+
+inline f16 h_val(uint16_t u)
+{
+    f16 h;
+    std::memcpy(&h, &u, 2);
+    return h;
+}
+inline uint16_t h_bits(f16 h)
+{
+    uint16_t u;
+    std::memcpy(&u, &h, 2);
+    return u;
+}
+inline uint16_t h_add(uint16_t a, uint16_t b) { return h_bits((f16)((float)h_val(a) + (float)h_val(b))); }
+inline uint16_t h_sub(uint16_t a, uint16_t b) { return h_bits((f16)((float)h_val(a) - (float)h_val(b))); }
+inline uint16_t h_mul(uint16_t a, uint16_t b) { return h_bits((f16)((float)h_val(a) * (float)h_val(b))); }
+// min(max(x, -1024), 1024) by comparisons: -0.0 and subnormals pass unchanged, +-inf clamp
+inline uint16_t h_clamp_v(uint16_t x)
+{
+    const float v = (float)h_val(x);
+    return v < -1024.0f ? (uint16_t)(H_VSAT | 0x8000) : (v > 1024.0f ? H_VSAT : x);
+}
+// the constant a check sends back for the magnitude x (x >= +0, so x orders as u16)
+inline uint16_t h_cst(uint16_t x, int algo, uint16_t beta)
+{
+    uint16_t r;
+    if (algo == LDPC_ALGO_NMS) {
+        r = h_mul(x, beta);
+    } else {
+        r = h_sub(x, beta);
+        if (!((float)h_val(r) > 0.0f)) r = 0;   // max(x - beta, +0)
+    }
+    return (float)h_val(r) > 256.0f ? H_MSAT : r;
+}
+
+// one codeword, binary16: decode_one_f32 with the changes of the half contract;
+// returns the iterations run, V holds the soft output
+int decode_one_f16(const ldpc_code *h, const uint16_t *llr, uint8_t *hard, int iters, int algo, uint16_t beta,
+                   bool early, std::vector<uint16_t> &V, std::vector<uint16_t> &msg)
+{
+    V.resize((size_t)h->n);
+    for (int i = 0; i < h->n; i++) V[i] = h_clamp_v(llr[i]);
+    msg.assign((size_t)h->e, 0);
+    uint16_t c[64], a[64];
+    int it = 0;
+    while (it < iters) {
+        size_t e0 = 0;
+        for (int i = 0; i < h->m; i++) {
+            const int d = h->check_deg[i];
+            const uint32_t *ev = &h->edge_var[h->check_start[i]];
+            uint16_t *mp = &msg[e0];
+            uint16_t sign = (d & 1) ? 0x8000 : 0;
+            uint16_t min1 = H_INF, min2 = H_INF;
+            for (int j = 0; j < d; j++) {
+                c[j] = h_sub(V[ev[j]], mp[j]);
+                a[j] = c[j] & 0x7FFF;
+                sign ^= c[j] & 0x8000;   // the sign of a contribution is its sign bit
+                const uint16_t t = min1;
+                min1 = std::min(a[j], min1);
+                min2 = std::min(min2, std::max(a[j], t));
+            }
+            const uint16_t cst1 = h_cst(min2, algo, beta), cst2 = h_cst(min1, algo, beta);
+            for (int j = 0; j < d; j++) {
+                const uint16_t r = a[j] == min1 ? cst1 : cst2;
+                const uint16_t m = (uint16_t)((r & 0x7FFF) | ((sign ^ c[j]) & 0x8000));
+                mp[j] = m;
+                V[ev[j]] = h_clamp_v(h_add(c[j], m));
+            }
+            e0 += (size_t)d;
+        }
+        it++;
+        if (early) {
+            bool ok = true;
+            for (int i = 0; i < h->m && ok; i++) {
+                int par = 0;
+                for (int j = 0; j < h->check_deg[i]; j++)
+                    par ^= (float)h_val(V[h->edge_var[h->check_start[i] + j]]) > 0.0f;
+                ok = par == 0;
+            }
+            if (ok) break;
+        }
+    }
+    for (int i = 0; i < h->n; i++) hard[i] = (float)h_val(V[i]) > 0.0f;
+    return it;
+}
+
 int host_threads_for(int units)
 {
     const char *e = getenv("LDPC_HOST_THREADS");
@@ -276,6 +367,28 @@ int host_decode_f32(const ldpc_code *h, const float *llr, uint8_t *hard, float *
         const int it = decode_one_f32(h, llr + (size_t)b * h->n, hard + (size_t)b * h->n, n_iter, algo, beta,
                                       p->early_term != 0, V[k], M[k]);
         if (soft) std::memcpy(soft + (size_t)b * h->n, V[k].data(), sizeof(float) * (size_t)h->n);
+        if (iters_used) iters_used[b] = it;
+    });
+    return LDPC_OK;
+}
+
+uint16_t host_f16_from_f32(float y)
+{
+    const float v = y < -1024.0f ? -1024.0f : (y > 1024.0f ? 1024.0f : y);
+    return h_bits((f16)v);   // round to nearest even
+}
+
+int host_decode_f16(const ldpc_code *h, const uint16_t *llr, uint8_t *hard, uint16_t *soft, int32_t *iters_used,
+                    int batch, int n_iter, const ldpc_params *p)
+{
+    const int algo = p->algo == LDPC_ALGO_NMS ? LDPC_ALGO_NMS : LDPC_ALGO_OMS;
+    const uint16_t beta = p->algo == LDPC_ALGO_MS ? (uint16_t)0 : (uint16_t)(h_bits((f16)p->beta) & 0x7FFF);
+    const int nt = host_threads_for(std::max(batch, 1));
+    std::vector<std::vector<uint16_t>> V((size_t)nt), M((size_t)nt);
+    parallel_units(batch, [&](int b, int k) {
+        const int it = decode_one_f16(h, llr + (size_t)b * h->n, hard + (size_t)b * h->n, n_iter, algo, beta,
+                                      p->early_term != 0, V[k], M[k]);
+        if (soft) std::memcpy(soft + (size_t)b * h->n, V[k].data(), sizeof(uint16_t) * (size_t)h->n);
         if (iters_used) iters_used[b] = it;
     });
     return LDPC_OK;

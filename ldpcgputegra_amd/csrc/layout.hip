@@ -13,6 +13,7 @@
 #include <algorithm>
 #include "kernels.h"
 #include "awgn_f32.h"
+#include "stairh.h"
 
 namespace {
 
@@ -57,6 +58,66 @@ __global__ void __launch_bounds__(256) deinterleave_k(const T *__restrict__ V, u
             if (hard) hard[(size_t)b * n + i] = (x > (T)0) ? 1 : 0;
             if (soft) soft[(size_t)b * n + i] = x;
         }
+    }
+}
+
+// binary16 (the half contract): the load clamps to +-1024 by
+// comparisons (-0.0 and subnormals pass unchanged), the store's hard decision
+// is V > 0 as a binary16 comparison (+-0 give 0).  Elements are 2-byte loads
+// and stores, so any 2-byte aligned buffer is taken.
+__global__ void __launch_bounds__(256) interleave_f16_k(const _Float16 *__restrict__ src, _Float16 *__restrict__ dst,
+                                                        int n, int batch, int stride)
+{
+    __shared__ _Float16 tile[64][66];
+    const int n0 = blockIdx.x * 64, b0 = blockIdx.y * 64;
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;   // 64 x 4
+    const _Float16 sat = (_Float16)1024.0f;
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int b = b0 + ty + 4 * r, i = n0 + tx;
+        _Float16 x = (b < batch && i < n) ? src[(size_t)b * n + i] : (_Float16)0.0f;
+        x = x < -sat ? -sat : (x > sat ? sat : x);
+        tile[ty + 4 * r][tx] = x;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int i = n0 + ty + 4 * r, b = b0 + tx;
+        if (i < n && b < stride) dst[(size_t)i * stride + b] = tile[tx][ty + 4 * r];
+    }
+}
+
+__global__ void __launch_bounds__(256) deinterleave_f16_k(const _Float16 *__restrict__ V, uint8_t *__restrict__ hard,
+                                                          _Float16 *__restrict__ soft, int n, int batch, int stride)
+{
+    __shared__ _Float16 tile[64][66];
+    const int n0 = blockIdx.x * 64, b0 = blockIdx.y * 64;
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int i = n0 + ty + 4 * r, b = b0 + tx;
+        tile[ty + 4 * r][tx] = (i < n && b < batch) ? V[(size_t)i * stride + b] : (_Float16)0.0f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int b = b0 + ty + 4 * r, i = n0 + tx;
+        if (b < batch && i < n) {
+            const _Float16 x = tile[tx][ty + 4 * r];
+            if (hard) hard[(size_t)b * n + i] = (x > (_Float16)0.0f) ? 1 : 0;
+            if (soft) soft[(size_t)b * n + i] = x;
+        }
+    }
+}
+
+// float -> binary16 LLR: clamp to +-1024, then round to nearest even
+__global__ void __launch_bounds__(256) convert_f32_f16_k(const float *__restrict__ y, _Float16 *__restrict__ h,
+                                                         long count)
+{
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (long)gridDim.x * blockDim.x) {
+        float v = y[i];
+        v = v < -1024.0f ? -1024.0f : (v > 1024.0f ? 1024.0f : v);
+        h[i] = (_Float16)v;
     }
 }
 
@@ -339,6 +400,27 @@ int launch_deinterleave_f32(const float *V, uint8_t *hard, float *soft, int n, i
 {
     dim3 g((n + 63) / 64, (batch + 63) / 64);
     hipLaunchKernelGGL(deinterleave_k<float>, g, dim3(256), 0, s, V, hard, soft, n, batch, stride);
+    return ok();
+}
+int launch_interleave_f16(const uint16_t *llr, uint16_t *V, int n, int batch, int stride, hipStream_t s)
+{
+    dim3 g((n + 63) / 64, (stride + 63) / 64);
+    hipLaunchKernelGGL(interleave_f16_k, g, dim3(256), 0, s, (const _Float16 *)llr, (_Float16 *)V, n, batch, stride);
+    return ok();
+}
+int launch_deinterleave_f16(const uint16_t *V, uint8_t *hard, uint16_t *soft, int n, int batch, int stride,
+                            hipStream_t s)
+{
+    dim3 g((n + 63) / 64, (batch + 63) / 64);
+    hipLaunchKernelGGL(deinterleave_f16_k, g, dim3(256), 0, s, (const _Float16 *)V, hard, (_Float16 *)soft, n, batch,
+                       stride);
+    return ok();
+}
+int launch_convert_f32_f16(const float *y, uint16_t *h, long count, hipStream_t s)
+{
+    if (count <= 0) return 0;
+    const long blocks = std::min<long>((count + 255) / 256, 256L * 64);
+    hipLaunchKernelGGL(convert_f32_f16_k, dim3((unsigned)blocks), dim3(256), 0, s, y, (_Float16 *)h, count);
     return ok();
 }
 int launch_interleave_grp_i8(const int8_t *llr, int8_t *V, int n, int batch, int stride, size_t gbytes,

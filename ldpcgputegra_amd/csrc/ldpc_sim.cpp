@@ -11,7 +11,7 @@
 //   ldpc_sim -code dvbs2_r1_2 -min 0.8 -max 1.2 -pas 0.1 -iter 50 -fer 100
 //            [-batch 4096] [-frames 1000000] [-OMS 1 | -NMS 29 | -MS]
 //            [-encoder [-fresh] | -gencoder [-fresh]] [-et] [-gpus N] [-seed S]
-//            [-kernel K] [-f32 [-beta B] | -f32q | -BP [-bpstair]]
+//            [-kernel K] [-f32 [-beta B] | -f32q | -BP [-bpstair] | -f16 [-beta B]]
 //
 // Three chains see the same noise (one u per element, the same first_cw and
 // seed scheme): the default draws the quantised int8 LLRs directly
@@ -28,7 +28,10 @@
 // -f32 runs keep 1.0; there is no int8 BP, so -BP with -f32q is a usage error.
 // -bpstair (with -BP only) lets BP run on the staircase kernel of the DVB-S2
 // codes (ldpc_ctx_set_bp_staircase): the same counts, many times the frames per
-// second; the JSON line names it ("bp_staircase").
+// second; the JSON line names it ("bp_staircase").  -f16 is the binary16 chain:
+// float channel -> ldpc_convert_f32_f16_async -> ldpc_decode_f16_async -> error
+// count, with -beta / -OMS / -NMS / -MS / -et as for -f32 (chain "f16"); a usage
+// error together with -f32, -f32q or -BP.
 //
 // -encoder alone draws 64 codewords once on the host and replicates them over
 // every batch; -encoder -fresh draws new information bits and encodes them on
@@ -62,6 +65,7 @@ struct Opt {
     int iter = 30, fer = 100, batch = 4096, gpus = 1, kernel = LDPC_KERNEL_AUTO;
     long frames = 1 << 20;
     bool encoder = false, gencoder = false, fresh = false, f32 = false, f32q = false, bp = false, bpstair = false;
+    bool f16 = false;
     ldpc_params p{};
     uint64_t seed = 1;
 };
@@ -109,10 +113,13 @@ void worker(int dev, const ldpc_code *h, const Opt &o, double sigma, Totals &tot
     int8_t *d_llr;
     float *d_y = nullptr;   // the float chains' channel output
     uint8_t *d_hard, *d_cw = nullptr;
+    uint16_t *d_h = nullptr;   // the binary16 chain's LLRs
     unsigned long long *d_cnt;
     (void)hipSetDevice(dev);
     if (hipMalloc(&d_llr, (size_t)o.batch * n) || hipMalloc(&d_hard, (size_t)o.batch * n) ||
-        hipMalloc(&d_cnt, 16) || ((o.f32 || o.f32q) && hipMalloc(&d_y, (size_t)o.batch * n * sizeof(float)))) {
+        hipMalloc(&d_cnt, 16) ||
+        ((o.f32 || o.f32q || o.f16) && hipMalloc(&d_y, (size_t)o.batch * n * sizeof(float))) ||
+        (o.f16 && hipMalloc(&d_h, (size_t)o.batch * n * sizeof(uint16_t)))) {
         fprintf(stderr, "hipMalloc failed\n");
         exit(1);
     }
@@ -146,6 +153,11 @@ void worker(int dev, const ldpc_code *h, const Opt &o, double sigma, Totals &tot
             CHECK(ldpc_awgn_f32_async(ctx, stream, d_y, o.batch, first, o.seed, sigma, 1.0, norm, d_cw));
             CHECK(ldpc_decode_f32_count_async(ctx, stream, d_y, d_hard, nullptr, nullptr, o.batch, o.iter, &o.p, k,
                                               d_cw, d_cnt));
+        } else if (o.f16) {
+            CHECK(ldpc_awgn_f32_async(ctx, stream, d_y, o.batch, first, o.seed, sigma, 1.0, 1.0, d_cw));
+            CHECK(ldpc_convert_f32_f16_async(ctx, stream, d_y, d_h, (long)o.batch * n));
+            CHECK(ldpc_decode_f16_async(ctx, stream, d_h, d_hard, nullptr, nullptr, o.batch, o.iter, &o.p));
+            CHECK(ldpc_count_errors_async(ctx, stream, d_hard, o.batch, k, d_cw, d_cnt));
         } else {
             if (o.f32q) {
                 CHECK(ldpc_awgn_f32_async(ctx, stream, d_y, o.batch, first, o.seed, sigma, 1.0, 1.0, d_cw));
@@ -168,6 +180,7 @@ void worker(int dev, const ldpc_code *h, const Opt &o, double sigma, Totals &tot
     }
     (void)hipFree(d_llr);
     if (d_y) (void)hipFree(d_y);
+    if (d_h) (void)hipFree(d_h);
     (void)hipFree(d_hard);
     (void)hipFree(d_cnt);
     if (d_cw) (void)hipFree(d_cw);
@@ -206,6 +219,7 @@ int main(int argc, char **argv)
         else if (a == "-et") o.p.early_term = 1;
         else if (a == "-f32") o.f32 = true;
         else if (a == "-f32q") o.f32q = true;
+        else if (a == "-f16") o.f16 = true;
         else if (a == "-beta") o.p.beta = (float)atof(nxt());
         else {
             fprintf(stderr, "unknown option %s\n", a.c_str());
@@ -220,6 +234,11 @@ int main(int argc, char **argv)
     if (o.f32 && o.f32q) {
         fprintf(stderr, "usage: -f32 (float channel -> float decode) and -f32q (float channel -> quantise -> int8 "
                         "decode) exclude each other\n");
+        return 2;
+    }
+    if (o.f16 && (o.f32 || o.f32q || o.bp)) {
+        fprintf(stderr, "usage: -f16 (float channel -> binary16 conversion -> binary16 decode) excludes -f32, -f32q "
+                        "and -BP\n");
         return 2;
     }
     if (o.bp) {   // belief propagation: the float chain, whatever -OMS / -NMS / -MS said
@@ -266,7 +285,7 @@ int main(int argc, char **argv)
         if (genc) CHECK(ldpc_encode(genc, info.data(), pool.data(), pool_n));
         else CHECK(ldpc_dvbs2_encode(h, info.data(), pool.data(), pool_n));
     }
-    const char *chain = o.f32 ? "f32" : (o.f32q ? "f32q" : "i8");
+    const char *chain = o.f16 ? "f16" : o.f32 ? "f32" : (o.f32q ? "f32q" : "i8");
     const char *algo = o.p.algo == LDPC_ALGO_BP    ? "BP"
                        : o.p.algo == LDPC_ALGO_NMS ? "NMS"
                                                    : (o.p.algo == LDPC_ALGO_MS ? "MS" : "OMS");

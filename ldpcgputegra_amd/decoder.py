@@ -77,7 +77,9 @@ class Decoder:
         11 = stairf (float staircase codes, DVB-S2: the float default for them,
         with or without early termination -- with it, one launch per iteration
         plus a syndrome pass, as include/ldpc_mi355x.h states; ALGO_BP runs on it
-        after set_bp_staircase(True)).  4 and 6 (windowed2 S = 32, coop2) were
+        after set_bp_staircase(True); the binary16 decode, decode_f16_device,
+        always runs on its packed half-precision element type and takes 0 or
+        11 only).  4 and 6 (windowed2 S = 32, coop2) were
         superseded and removed."""
         _lib.check(_lib.lib().ldpc_ctx_set_kernel(self._ctx, int(kernel)))
 
@@ -185,6 +187,43 @@ class Decoder:
                                                    iters.ctypes.data, B, n_iter, C.byref(p)))
         return hard, soft, iters
 
+    @staticmethod
+    def _f16_host(llr):
+        """float16 array (or its uint16 bit patterns), contiguous"""
+        llr = np.asarray(llr)
+        if llr.dtype == np.uint16:
+            llr = llr.view(np.float16)
+        return np.ascontiguousarray(llr, dtype=np.float16)
+
+    def decode_f16(self, llr, n_iter, params=None, out=None):
+        """binary16 decode of host arrays (``ldpc_decode_f16``): llr float16
+        [batch, N] (or uint16 bit patterns).  A GPU context copies in, decodes
+        on the packed staircase kernel (staircase codes only) and copies out; a
+        host context (device=-1) runs the host decoder, on any code."""
+        llr = self._f16_host(llr)
+        B = llr.shape[0] if llr.ndim == 2 else 1
+        assert llr.size == B * self.code.n
+        hard = out if out is not None else np.empty((B, self.code.n), dtype=np.uint8)
+        p = params or _lib.default_params(algo=_lib.ALGO_MS)
+        _lib.check(_lib.lib().ldpc_decode_f16(self._ctx, llr.ctypes.data, hard.ctypes.data, B, n_iter, C.byref(p)))
+        return hard
+
+    def decode_f16_soft(self, llr, n_iter, params=None):
+        """Host context (device=-1) only: (hard, soft, iters_used) of the
+        binary16 decode, soft as float16 -- the definition of the half contract
+        that decode_f16_device's outputs are compared with
+        (``ldpc_decode_f16_soft``)."""
+        llr = self._f16_host(llr)
+        B = llr.shape[0] if llr.ndim == 2 else 1
+        assert llr.size == B * self.code.n
+        hard = np.empty((B, self.code.n), dtype=np.uint8)
+        soft = np.empty((B, self.code.n), dtype=np.float16)
+        iters = np.empty(B, dtype=np.int32)
+        p = params or _lib.default_params(algo=_lib.ALGO_MS)
+        _lib.check(_lib.lib().ldpc_decode_f16_soft(self._ctx, llr.ctypes.data, hard.ctypes.data, soft.ctypes.data,
+                                                   iters.ctypes.data, B, n_iter, C.byref(p)))
+        return hard, soft, iters
+
     # -- host buffers, asynchronous (H2D -> decode -> D2H queued on `stream`)
     def decode_i8_host_async(self, llr, hard, n_iter, params=None, stream=None):
         """Queue the decode of host (preferably pinned_empty) arrays llr -> hard
@@ -250,6 +289,28 @@ class Decoder:
         self._on_stream(stream, lambda s: _lib.check(_lib.lib().ldpc_decode_f32_async(
             self._ctx, s, self._ptr(llr), self._ptr(hard), self._ptr(soft), self._ptr(iters_used), B, n_iter,
             C.byref(p))), self.device)
+
+    def decode_f16_device(self, llr, hard, n_iter, params=None, soft=None, iters_used=None, stream=None):
+        """binary16 decode of device tensors (``ldpc_decode_f16_async``): llr
+        and soft torch.float16 [batch, N], on the packed half-precision
+        staircase kernel (DVB-S2 and like-shaped codes)."""
+        import torch
+        B = llr.shape[0]
+        assert llr.dtype == torch.float16 and (soft is None or soft.dtype == torch.float16)
+        assert llr.numel() == B * self.code.n and llr.is_contiguous()
+        p = params or _lib.default_params(algo=_lib.ALGO_MS)
+        self._on_stream(stream, lambda s: _lib.check(_lib.lib().ldpc_decode_f16_async(
+            self._ctx, s, self._ptr(llr), self._ptr(hard), self._ptr(soft), self._ptr(iters_used), B, n_iter,
+            C.byref(p))), self.device)
+
+    def convert_f16_device(self, y, h, stream=None):
+        """float32 -> binary16 LLRs on the device: h = RNE16(clamp(y, +-1024)),
+        channel.convert_f16_host's twin (``ldpc_convert_f32_f16_async``)."""
+        import torch
+        assert y.dtype == torch.float32 and h.dtype == torch.float16
+        assert y.is_contiguous() and h.is_contiguous() and y.numel() == h.numel()
+        self._on_stream(stream, lambda s: _lib.check(_lib.lib().ldpc_convert_f32_f16_async(
+            self._ctx, s, self._ptr(y), self._ptr(h), y.numel())), self.device)
 
     def boxplus_device(self, a, b, out, stream=None):
         """out = a [+] b element by element on the device (float32 tensors of
