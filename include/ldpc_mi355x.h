@@ -391,6 +391,29 @@ int ldpc_boxplus_f32_async(ldpc_ctx *ctx, void *hip_stream, const float *d_a, co
  * 2^32 with stride = batch rounded up to 64 (33088 codewords at n = 64800,
  * twice float32's limit).  LDPC_STAIRF_S forces the group width as for float32.
  *
+ * ldpc_ctx_set_f16_all_codes(ctx, 1) (off by default; ldpc_ctx_get_f16_all_codes
+ * reads it back; both work on GPU and host contexts, and a host context
+ * decodes every code either way) opens the GPU decode to every code, on two
+ * more kernels of the same contract and the same two-codewords-per-lane
+ * packing.  With the switch on:
+ *   LDPC_KERNEL_AUTO  a staircase code runs on LDPC_KERNEL_STAIRF as before; any
+ *                     other code on LDPC_KERNEL_LDS where the float32 decode
+ *                     would prefer it (the pairs' state fits LDS and the layers
+ *                     are wide enough), else on LDPC_KERNEL_GENERIC;
+ *   forced 7          the packed LDS-resident kernel (`ldsh`) where the state
+ *                     fits LDS (lds_f32 of ldpc_code_layer_info), else
+ *                     LDPC_EUNSUPPORTED;
+ *   forced 1          the packed any-H kernel (`generich`), on any code;
+ *   forced 11         as with the switch off;
+ *   any other family  LDPC_EUNSUPPORTED, "not applicable".
+ * ldpc_ctx_last_kernel reports the family that ran, ldpc_ctx_last_skipped 0.
+ * On LDPC_KERNEL_LDS ldpc_ctx_last_lds_shape reports lanes per PAIR of
+ * codewords and two lanes per check or not; the environment variable
+ * LDPC_LDSH_LANES (8, 16, 32 or 64) forces the lanes per pair, and a value the
+ * code cannot run (fewer lanes than its widest layer needs, or a wave's pairs
+ * passing 64 KB of LDS) is LDPC_EUNSUPPORTED before any launch.  With the switch
+ * off every call behaves as if it did not exist.
+ *
  * ldpc_decode_f16: host buffers, synchronous: copy in, decode, copy out on a
  * GPU context; the host decoder, which takes every code, on a device -1
  * context (last_kernel LDPC_KERNEL_HOST).
@@ -403,6 +426,8 @@ int ldpc_decode_f16(ldpc_ctx *ctx, const uint16_t *llr, uint8_t *hard, int batch
                     const ldpc_params *p);
 int ldpc_decode_f16_soft(ldpc_ctx *ctx, const uint16_t *llr, uint8_t *hard, uint16_t *soft, int32_t *iters_used,
                          int batch, int n_iter, const ldpc_params *p);
+int ldpc_ctx_set_f16_all_codes(ldpc_ctx *ctx, int enable);
+int ldpc_ctx_get_f16_all_codes(ldpc_ctx *ctx, int *enable);
 /* float32 -> binary16 LLRs: h = RNE16(min(max(y, -1024), 1024)).  _host needs
  * no context; _async runs on the device of a GPU context (a host context is
  * LDPC_EUNSUPPORTED), bit for bit the host's results.  count = 0 touches
@@ -414,6 +439,12 @@ int ldpc_convert_f32_f16_async(ldpc_ctx *ctx, void *hip_stream, const float *d_y
  * `widths` (bit S set: the code has that table; 0: none).  Introspection for
  * tools/f16_rate.py, which holds the rule against measured times. */
 int ldpc_f16_staircase_width_rule(int stride, unsigned widths);
+/* log2 of the lanes per pair (3 .. 6) the binary16 LDS-resident kernel's rule
+ * picks for `pairs` pairs of codewords ((batch + 1) / 2) of a code with n
+ * variables, e edges and max_width checks in its widest layer: a cost model
+ * fitted to measured runs.  Introspection for
+ * tools/f16_short_rate.py and the tests, which restate it. */
+int ldpc_f16_lds_shape_rule(int n, int e, int max_width, int pairs);
 
 /* ---- mixed-rate batches (BASELINE config 5) ---------------------------- */
 /* A batch whose codewords use different codes of equal length N (e.g. the

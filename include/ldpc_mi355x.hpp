@@ -93,6 +93,14 @@ public:
         check(ldpc_ctx_get_bp_staircase(ctx_, &on));
         return on != 0;
     }
+    // the binary16 decode on every code, not the staircase ones alone (ldpc_ctx_set_f16_all_codes; off by default)
+    void setF16AllCodes(bool on) { check(ldpc_ctx_set_f16_all_codes(ctx_, on ? 1 : 0)); }
+    bool f16AllCodes()
+    {
+        int on = 0;
+        check(ldpc_ctx_get_f16_all_codes(ctx_, &on));
+        return on != 0;
+    }
     ldpc_ctx *context() { return ctx_; }
 
 protected:

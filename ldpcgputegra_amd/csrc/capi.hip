@@ -171,6 +171,20 @@ extern "C" int ldpc_ctx_get_bp_staircase(ldpc_ctx *c, int *enable)
     return LDPC_OK;
 }
 
+extern "C" int ldpc_ctx_set_f16_all_codes(ldpc_ctx *c, int enable)
+{
+    if (!c) return ldpc_set_error(LDPC_EINVAL, "NULL ctx");
+    c->f16_all_codes = enable != 0;   // (a host context decodes every code either way)
+    return LDPC_OK;
+}
+
+extern "C" int ldpc_ctx_get_f16_all_codes(ldpc_ctx *c, int *enable)
+{
+    if (!c || !enable) return ldpc_set_error(LDPC_EINVAL, "NULL");
+    *enable = c->f16_all_codes ? 1 : 0;
+    return LDPC_OK;
+}
+
 extern "C" int ldpc_ctx_profile(ldpc_ctx *c, int enable)
 {
     if (!c) return ldpc_set_error(LDPC_EINVAL, "NULL ctx");

@@ -3,16 +3,21 @@
 // the host decoder's twin with soft output, and the float -> binary16
 // conversion.  binary16 travels as uint16_t bit patterns.  Host code only.
 //
-// The f16 decode has one GPU kernel, so it does not go through dispatch.hip's
-// selection: a code stairf_upload accepts runs on it (reported as
-// LDPC_KERNEL_STAIRF, another element type of that family), any other code is
-// LDPC_EUNSUPPORTED on a GPU context.  The scratch is the context's own (the V
-// and message buffers the other element types use, grown as needed).
+// The f16 decode has a selection of its own (pick_f16 below), not dispatch.hip's.
+// By default it has one GPU kernel: a code stairf_upload accepts runs on stairh
+// (reported as LDPC_KERNEL_STAIRF, another element type of that family), any
+// other code is LDPC_EUNSUPPORTED on a GPU context.  With
+// ldpc_ctx_set_f16_all_codes on, the other codes run on the packed LDS-resident
+// kernel (ldsh, reported as LDPC_KERNEL_LDS) or the packed any-H kernel
+// (generich, LDPC_KERNEL_GENERIC), which can also be forced on any code.  The
+// scratch is the context's own (the V and message buffers the other element
+// types use, grown as needed).
 #include <cmath>
 #include <cstring>
 
 #include "ctx.h"
 #include "host.h"
+#include "ldsh.h"
 #include "stairh.h"
 
 namespace {
@@ -32,6 +37,32 @@ int check_params_f16(const ldpc_ctx *c, int batch, int n_iter, const ldpc_params
     return LDPC_OK;
 }
 
+// the kernel family of this call, or a status < 0 with the error set.  Switch
+// off: the staircase kernel or nothing, as before the switch existed.
+int pick_f16(const ldpc_ctx *c)
+{
+    const ldpc_code *h = c->code;
+    const bool automatic = c->kernel == LDPC_KERNEL_AUTO;
+    if (!c->f16_all_codes) {
+        if (!c->stairf.valid)
+            return ldpc_set_error(LDPC_EUNSUPPORTED, "the binary16 decode runs on the staircase kernel only (DVB-S2 and "
+                                  "like-shaped codes); this %dx%d code has no staircase table: decode it in float32, or in "
+                                  "binary16 on a host context", h->n, h->m);
+        if (!automatic && c->kernel != LDPC_KERNEL_STAIRF)
+            return ldpc_set_error(LDPC_EUNSUPPORTED, "kernel %d selected but not applicable to a binary16 decode",
+                                  c->kernel);
+        return LDPC_KERNEL_STAIRF;
+    }
+    if (automatic) {
+        if (c->stairf.valid) return LDPC_KERNEL_STAIRF;
+        return lds_preferred(h, c->lds, true) ? LDPC_KERNEL_LDS : LDPC_KERNEL_GENERIC;
+    }
+    if (c->kernel == LDPC_KERNEL_GENERIC) return LDPC_KERNEL_GENERIC;
+    if (c->kernel == LDPC_KERNEL_LDS && lds_applicable(h, c->lds, true)) return LDPC_KERNEL_LDS;
+    if (c->kernel == LDPC_KERNEL_STAIRF && c->stairf.valid) return LDPC_KERNEL_STAIRF;
+    return ldpc_set_error(LDPC_EUNSUPPORTED, "kernel %d selected but not applicable to a binary16 decode", c->kernel);
+}
+
 int decode_f16_device(ldpc_ctx *c, Scratch &sc, hipStream_t s, const uint16_t *d_llr, uint8_t *d_hard, uint16_t *d_soft,
                       int32_t *d_iters, int batch, int n_iter, const ldpc_params *p)
 {
@@ -42,40 +73,17 @@ int decode_f16_device(ldpc_ctx *c, Scratch &sc, hipStream_t s, const uint16_t *d
         return ldpc_set_error(LDPC_EINVAL, "binary16 buffers must be 2-byte aligned");
     if (batch == 0) return LDPC_OK;
     const ldpc_code *h = c->code;
-    if (!c->stairf.valid)
-        return ldpc_set_error(LDPC_EUNSUPPORTED, "the binary16 decode runs on the staircase kernel only (DVB-S2 and "
-                              "like-shaped codes); this %dx%d code has no staircase table: decode it in float32, or in "
-                              "binary16 on a host context", h->n, h->m);
-    if (c->kernel != LDPC_KERNEL_AUTO && c->kernel != LDPC_KERNEL_STAIRF)
-        return ldpc_set_error(LDPC_EUNSUPPORTED, "kernel %d selected but not applicable to a binary16 decode",
-                              c->kernel);
-    const int stride = (batch + 63) / 64 * 64;
-    if (!stairh_stride_ok(c->stairf, h->n, stride))
-        return ldpc_set_error(LDPC_EUNSUPPORTED, "binary16 decode: batch %d of n = %d passes the kernel's 32-bit V "
-                              "offsets ((n + 1) * stride * 2 < 2^32); split the batch", batch, h->n);
-    HIP_TRY(hipSetDevice(c->device));
-    c->last_kernel = LDPC_KERNEL_STAIRF;
-    c->last_skipped = 0;
-    c->last_lds_lanes = c->last_lds_split = 0;
-    c->last_et_stage = 0;
-    const bool early = p->early_term != 0;
-    const size_t msg_bytes = stairh_msg_bytes(c->stairf, stride);
-    if ((rc = ensure(&sc.d_V, &sc.V_bytes, stairh_v_bytes(h->n, stride))) != LDPC_OK ||
-        (rc = ensure(&sc.d_msg, &sc.msg_bytes, msg_bytes + 4096)) != LDPC_OK ||
-        (rc = ensure(&sc.d_early, &sc.early_bytes, early ? (size_t)stride * 12 : 0)) != LDPC_OK)
-        return rc;
-    HIP_TRY(hipMemsetAsync(sc.d_msg, 0, msg_bytes, s));   // messages start at +0
-    if (launch_interleave_f16(d_llr, (uint16_t *)sc.d_V, h->n, batch, stride, s))
-        return ldpc_set_error(LDPC_EDEVICE, "interleave: %s", hipGetErrorString(hipGetLastError()));
-    const bool ms = p->algo == LDPC_ALGO_MS;
+    const int kern = pick_f16(c);
+    if (kern < 0) return kern;
+    const bool ms = p->algo == LDPC_ALGO_MS, early = p->early_term != 0;
     DecodeLaunch L{};
-    L.V = sc.d_V;
-    L.msg = sc.d_msg;
-    L.stride = L.vpitch = stride;
     L.batch = batch;
     L.iters = n_iter;
     L.is_float = 1;
     L.d_edge_var = c->d_edge_var;
+    L.d_group_deg = c->d_group_deg;
+    L.d_group_cnt = c->d_group_cnt;
+    L.n_groups = h->n_groups;
     L.n = h->n;
     L.m = h->m;
     L.e = h->e;
@@ -83,10 +91,54 @@ int decode_f16_device(ldpc_ctx *c, Scratch &sc, hipStream_t s, const uint16_t *d
     L.beta = ms ? 0.0f : p->beta;
     L.early = early;
     L.iters_used = d_iters;
-    if (early) {   // (iterations used land in the scratch when the caller passed no array)
-        L.bad = (uint32_t *)sc.d_early;
-        if (!L.iters_used) L.iters_used = (int32_t *)((char *)sc.d_early + (size_t)stride * 4);
-        L.live = (uint8_t *)sc.d_early + (size_t)stride * 8;
+    // checks that refuse come before anything is allocated, read or recorded
+    int stride = 0, lg = 0, split = 0;
+    if (kern == LDPC_KERNEL_STAIRF) {
+        stride = (batch + 63) / 64 * 64;
+        if (!stairh_stride_ok(c->stairf, h->n, stride))
+            return ldpc_set_error(LDPC_EUNSUPPORTED, "binary16 decode: batch %d of n = %d passes the kernel's 32-bit V "
+                                  "offsets ((n + 1) * stride * 2 < 2^32); split the batch", batch, h->n);
+    } else if (kern == LDPC_KERNEL_LDS) {
+        if (ldsh_shape(h, c->lds, batch, &lg, &split))
+            return ldpc_set_error(LDPC_EUNSUPPORTED, "binary16 decode: LDPC_LDSH_LANES asks for a shape this %dx%d code "
+                                  "cannot run (its widest layer needs %d lanes per pair, and the state of the pairs of "
+                                  "a wave must fit 64 KB of LDS)", h->n, h->m, 1 << c->lds.lpc_log2);
+    } else {
+        stride = generich_stride(batch);
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    c->last_kernel = kern;
+    c->last_skipped = 0;
+    c->last_lds_lanes = c->last_lds_split = 0;
+    c->last_et_stage = 0;
+    if (kern == LDPC_KERNEL_LDS) {   // frame-major in and out, the whole state in LDS: no scratch
+        c->last_lds_lanes = 1 << lg;
+        c->last_lds_split = split;
+    } else {
+        size_t v_bytes, msg_bytes, early_bytes = 0;
+        if (kern == LDPC_KERNEL_STAIRF) {
+            v_bytes = stairh_v_bytes(h->n, stride);
+            msg_bytes = stairh_msg_bytes(c->stairf, stride);
+            early_bytes = early ? (size_t)stride * 12 : 0;
+        } else {
+            v_bytes = (size_t)h->n * stride * 2;
+            msg_bytes = (size_t)h->e * stride * 2;
+        }
+        if ((rc = ensure(&sc.d_V, &sc.V_bytes, v_bytes)) != LDPC_OK ||
+            (rc = ensure(&sc.d_msg, &sc.msg_bytes, msg_bytes + 4096)) != LDPC_OK ||
+            (rc = ensure(&sc.d_early, &sc.early_bytes, early_bytes)) != LDPC_OK)
+            return rc;
+        HIP_TRY(hipMemsetAsync(sc.d_msg, 0, msg_bytes, s));   // messages start at +0
+        if (launch_interleave_f16(d_llr, (uint16_t *)sc.d_V, h->n, batch, stride, s))
+            return ldpc_set_error(LDPC_EDEVICE, "interleave: %s", hipGetErrorString(hipGetLastError()));
+        L.V = sc.d_V;
+        L.msg = sc.d_msg;
+        L.stride = L.vpitch = stride;
+        if (early && kern == LDPC_KERNEL_STAIRF) {   // (iterations used land in the scratch when the caller passed no array)
+            L.bad = (uint32_t *)sc.d_early;
+            if (!L.iters_used) L.iters_used = (int32_t *)((char *)sc.d_early + (size_t)stride * 4);
+            L.live = (uint8_t *)sc.d_early + (size_t)stride * 8;
+        }
     }
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     if (c->profile) {
@@ -94,7 +146,9 @@ int decode_f16_device(ldpc_ctx *c, Scratch &sc, hipStream_t s, const uint16_t *d
         HIP_TRY(hipEventCreate(&ev1));
         HIP_TRY(hipEventRecord(ev0, s));
     }
-    const int lr = launch_stairh(L, c->stairf, s);
+    const int lr = kern == LDPC_KERNEL_STAIRF ? launch_stairh(L, c->stairf, s)
+                   : kern == LDPC_KERNEL_LDS  ? launch_ldsh(c->lds, h, d_llr, d_hard, d_soft, L, lg, split, s)
+                                              : launch_generich(L, s);
     if (c->profile) {
         HIP_TRY(hipEventRecord(ev1, s));
         c->events.emplace_back(ev0, ev1);
@@ -104,7 +158,8 @@ int decode_f16_device(ldpc_ctx *c, Scratch &sc, hipStream_t s, const uint16_t *d
         const char *why = e != hipSuccess ? hipGetErrorString(e) : "launch configuration rejected by the host side";
         return ldpc_set_error(LDPC_EDEVICE, "binary16 decode launch: %s", why);
     }
-    if ((d_hard || d_soft) && launch_deinterleave_f16((const uint16_t *)sc.d_V, d_hard, d_soft, h->n, batch, stride, s))
+    if (kern != LDPC_KERNEL_LDS && (d_hard || d_soft) &&
+        launch_deinterleave_f16((const uint16_t *)sc.d_V, d_hard, d_soft, h->n, batch, stride, s))
         return ldpc_set_error(LDPC_EDEVICE, "deinterleave: %s", hipGetErrorString(hipGetLastError()));
     return LDPC_OK;
 }

@@ -54,7 +54,7 @@ def boxplus_host(a, b):
 class Decoder:
     """One C-ABI decoder context (device scratch for ``max_batch`` codewords)."""
 
-    def __init__(self, code, device=0, max_batch=4096, kernel=0, bp_staircase=False):
+    def __init__(self, code, device=0, max_batch=4096, kernel=0, bp_staircase=False, f16_all_codes=False):
         self.code = code if isinstance(code, Code) else Code(code)
         self.device = device
         self.max_batch = max_batch
@@ -66,6 +66,8 @@ class Decoder:
             self.set_kernel(kernel)
         if bp_staircase:
             self.set_bp_staircase(True)
+        if f16_all_codes:
+            self.set_f16_all_codes(True)
 
     # -- configuration
     def set_kernel(self, kernel):
@@ -78,8 +80,9 @@ class Decoder:
         with or without early termination -- with it, one launch per iteration
         plus a syndrome pass, as include/ldpc_mi355x.h states; ALGO_BP runs on it
         after set_bp_staircase(True); the binary16 decode, decode_f16_device,
-        always runs on its packed half-precision element type and takes 0 or
-        11 only).  4 and 6 (windowed2 S = 32, coop2) were
+        runs on its packed half-precision element type and takes 0 or 11 only,
+        until set_f16_all_codes(True) adds the packed binary16 element types of 7
+        and 1).  4 and 6 (windowed2 S = 32, coop2) were
         superseded and removed."""
         _lib.check(_lib.lib().ldpc_ctx_set_kernel(self._ctx, int(kernel)))
 
@@ -102,6 +105,23 @@ class Decoder:
     def bp_staircase(self):
         on = C.c_int()
         _lib.check(_lib.lib().ldpc_ctx_get_bp_staircase(self._ctx, C.byref(on)))
+        return bool(on.value)
+
+    def set_f16_all_codes(self, flag):
+        """Let the binary16 decode (decode_f16_device, decode_f16) take every
+        code on the GPU, not the staircase ones alone: a code without a staircase
+        table then runs on the packed LDS-resident kernel (7, ``last_kernel``
+        "lds") where the float decode would prefer 7, else on the packed any-H
+        kernel (1, "generic"); set_kernel(7) and set_kernel(1) force them, 1 on
+        any code.  Off (the default) those codes are LDPC_EUNSUPPORTED.  Works on
+        a host decoder too, which decodes every code either way
+        (``ldpc_ctx_set_f16_all_codes``)."""
+        _lib.check(_lib.lib().ldpc_ctx_set_f16_all_codes(self._ctx, int(bool(flag))))
+
+    @property
+    def f16_all_codes(self):
+        on = C.c_int()
+        _lib.check(_lib.lib().ldpc_ctx_get_f16_all_codes(self._ctx, C.byref(on)))
         return bool(on.value)
 
     def profile(self, enable=True):
