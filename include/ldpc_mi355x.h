@@ -414,6 +414,23 @@ int ldpc_boxplus_f32_async(ldpc_ctx *ctx, void *hip_stream, const float *d_a, co
  * passing 64 KB of LDS) is LDPC_EUNSUPPORTED before any launch.  With the switch
  * off every call behaves as if it did not exist.
  *
+ * ldpc_ctx_set_f16_edge_parallel(ctx, 1) (off by default;
+ * ldpc_ctx_get_f16_edge_parallel reads it back) is a second, independent
+ * switch: it lets the binary16 decode run LDPC_KERNEL_LDSEP, the edge-parallel
+ * kernel of the short quasi-cyclic codes (802.11n 648x324, 576x288 and tables
+ * of their shape) in binary16 (`ldseph`: one wave per pair of codewords, one
+ * lane per edge, the same contract, equal to the host decoder bit for bit, the
+ * sign of zero soft values included).  Setting it is LDPC_EUNSUPPORTED, with
+ * the setting left as it was, on a host context and on a code for which
+ * ldpc_ctx_set_kernel(ctx, LDPC_KERNEL_LDSEP) fails.  With it on, where the
+ * float32 decode could run LDPC_KERNEL_LDSEP (the pairs of a workgroup fit
+ * LDS), LDPC_KERNEL_AUTO and a forced 9 run it -- it is checked first, as for
+ * float32 -- and ldpc_ctx_last_kernel reports LDPC_KERNEL_LDSEP,
+ * ldpc_ctx_last_skipped 0, ldpc_ctx_last_lds_shape 0 / 0; the decode allocates
+ * nothing.  Every other setting is decided exactly as with this switch off,
+ * whatever ldpc_ctx_set_f16_all_codes says.  With the switch off a forced 9 is
+ * LDPC_EUNSUPPORTED as before.
+ *
  * ldpc_decode_f16: host buffers, synchronous: copy in, decode, copy out on a
  * GPU context; the host decoder, which takes every code, on a device -1
  * context (last_kernel LDPC_KERNEL_HOST).
@@ -428,6 +445,8 @@ int ldpc_decode_f16_soft(ldpc_ctx *ctx, const uint16_t *llr, uint8_t *hard, uint
                          int batch, int n_iter, const ldpc_params *p);
 int ldpc_ctx_set_f16_all_codes(ldpc_ctx *ctx, int enable);
 int ldpc_ctx_get_f16_all_codes(ldpc_ctx *ctx, int *enable);
+int ldpc_ctx_set_f16_edge_parallel(ldpc_ctx *ctx, int enable);
+int ldpc_ctx_get_f16_edge_parallel(ldpc_ctx *ctx, int *enable);
 /* float32 -> binary16 LLRs: h = RNE16(min(max(y, -1024), 1024)).  _host needs
  * no context; _async runs on the device of a GPU context (a host context is
  * LDPC_EUNSUPPORTED), bit for bit the host's results.  count = 0 touches

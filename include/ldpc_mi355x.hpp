@@ -101,6 +101,15 @@ public:
         check(ldpc_ctx_get_f16_all_codes(ctx_, &on));
         return on != 0;
     }
+    // the binary16 decode on the edge-parallel kernel of the short QC codes (ldpc_ctx_set_f16_edge_parallel; off by
+    // default; throws on a host decoder or a code kernel family 9 cannot schedule)
+    void setF16EdgeParallel(bool on) { check(ldpc_ctx_set_f16_edge_parallel(ctx_, on ? 1 : 0)); }
+    bool f16EdgeParallel()
+    {
+        int on = 0;
+        check(ldpc_ctx_get_f16_edge_parallel(ctx_, &on));
+        return on != 0;
+    }
     ldpc_ctx *context() { return ctx_; }
 
 protected:

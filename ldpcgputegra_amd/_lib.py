@@ -89,6 +89,8 @@ SIGNATURES = {
     "ldpc_ctx_get_bp_staircase": (I, [P, C.POINTER(I)]),
     "ldpc_ctx_set_f16_all_codes": (I, [P, I]),
     "ldpc_ctx_get_f16_all_codes": (I, [P, C.POINTER(I)]),
+    "ldpc_ctx_set_f16_edge_parallel": (I, [P, I]),
+    "ldpc_ctx_get_f16_edge_parallel": (I, [P, C.POINTER(I)]),
     "ldpc_f16_lds_shape_rule": (I, [I, I, I, I]),
     "ldpc_bp_staircase_width_model": (I, [I, I, I, C.c_uint]),
     "ldpc_ctx_last_kernel": (I, [P, C.POINTER(I)]),

@@ -11,7 +11,10 @@
 // kernel (ldsh, reported as LDPC_KERNEL_LDS) or the packed any-H kernel
 // (generich, LDPC_KERNEL_GENERIC), which can also be forced on any code.  The
 // scratch is the context's own (the V and message buffers the other element
-// types use, grown as needed).
+// types use, grown as needed).  ldpc_ctx_set_f16_edge_parallel, a switch of
+// its own, puts the edge-parallel kernel of the short QC codes in front of all
+// that (ldseph, LDPC_KERNEL_LDSEP): the automatic choice and a forced 9 where
+// the code fits it, every other setting decided as without it.
 #include <cmath>
 #include <cstring>
 
@@ -43,6 +46,9 @@ int pick_f16(const ldpc_ctx *c)
 {
     const ldpc_code *h = c->code;
     const bool automatic = c->kernel == LDPC_KERNEL_AUTO;
+    // checked first, as dispatch.hip does for float32; independent of f16_all_codes
+    if (c->f16_edge_parallel && (automatic || c->kernel == LDPC_KERNEL_LDSEP) && ldseph_applicable(h, c->lds))
+        return LDPC_KERNEL_LDSEP;
     if (!c->f16_all_codes) {
         if (!c->stairf.valid)
             return ldpc_set_error(LDPC_EUNSUPPORTED, "the binary16 decode runs on the staircase kernel only (DVB-S2 and "
@@ -103,18 +109,20 @@ int decode_f16_device(ldpc_ctx *c, Scratch &sc, hipStream_t s, const uint16_t *d
             return ldpc_set_error(LDPC_EUNSUPPORTED, "binary16 decode: LDPC_LDSH_LANES asks for a shape this %dx%d code "
                                   "cannot run (its widest layer needs %d lanes per pair, and the state of the pairs of "
                                   "a wave must fit 64 KB of LDS)", h->n, h->m, 1 << c->lds.lpc_log2);
-    } else {
+    } else if (kern == LDPC_KERNEL_GENERIC) {
         stride = generich_stride(batch);
-    }
+    }   // (ldseph has nothing to refuse)
     HIP_TRY(hipSetDevice(c->device));
     c->last_kernel = kern;
     c->last_skipped = 0;
     c->last_lds_lanes = c->last_lds_split = 0;
     c->last_et_stage = 0;
-    if (kern == LDPC_KERNEL_LDS) {   // frame-major in and out, the whole state in LDS: no scratch
+    // ldsh and ldseph: frame-major in and out, the whole state in LDS (and registers): no scratch
+    const bool resident = kern == LDPC_KERNEL_LDS || kern == LDPC_KERNEL_LDSEP;
+    if (kern == LDPC_KERNEL_LDS) {
         c->last_lds_lanes = 1 << lg;
         c->last_lds_split = split;
-    } else {
+    } else if (!resident) {
         size_t v_bytes, msg_bytes, early_bytes = 0;
         if (kern == LDPC_KERNEL_STAIRF) {
             v_bytes = stairh_v_bytes(h->n, stride);
@@ -148,6 +156,7 @@ int decode_f16_device(ldpc_ctx *c, Scratch &sc, hipStream_t s, const uint16_t *d
     }
     const int lr = kern == LDPC_KERNEL_STAIRF ? launch_stairh(L, c->stairf, s)
                    : kern == LDPC_KERNEL_LDS  ? launch_ldsh(c->lds, h, d_llr, d_hard, d_soft, L, lg, split, s)
+                   : kern == LDPC_KERNEL_LDSEP ? launch_ldseph(c->lds, h, d_llr, d_hard, d_soft, L, s)
                                               : launch_generich(L, s);
     if (c->profile) {
         HIP_TRY(hipEventRecord(ev1, s));
@@ -158,7 +167,7 @@ int decode_f16_device(ldpc_ctx *c, Scratch &sc, hipStream_t s, const uint16_t *d
         const char *why = e != hipSuccess ? hipGetErrorString(e) : "launch configuration rejected by the host side";
         return ldpc_set_error(LDPC_EDEVICE, "binary16 decode launch: %s", why);
     }
-    if (kern != LDPC_KERNEL_LDS && (d_hard || d_soft) &&
+    if (!resident && (d_hard || d_soft) &&
         launch_deinterleave_f16((const uint16_t *)sc.d_V, d_hard, d_soft, h->n, batch, stride, s))
         return ldpc_set_error(LDPC_EDEVICE, "deinterleave: %s", hipGetErrorString(hipGetLastError()));
     return LDPC_OK;

@@ -64,6 +64,7 @@ struct ldpc_ctx {
     int last_skipped = 0;   // the preferred kernel the last decode could not use at its batch size (0: none)
     bool bp_staircase = false;   // LDPC_ALGO_BP may run on the staircase kernel (ldpc_ctx_set_bp_staircase)
     bool f16_all_codes = false;  // the binary16 decode takes every code: ldsh / generich (ldpc_ctx_set_f16_all_codes)
+    bool f16_edge_parallel = false;   // the binary16 decode runs family 9 where it fits: ldseph (ldpc_ctx_set_f16_edge_parallel)
     int lds_pad = 0;        // extra dynamic LDS per windowed2 workgroup (ldpc_ctx_set_lds_pad)
     hipStream_t stream = nullptr;
     // device copy of the code

@@ -11,7 +11,7 @@
 //   ldpc_sim -code dvbs2_r1_2 -min 0.8 -max 1.2 -pas 0.1 -iter 50 -fer 100
 //            [-batch 4096] [-frames 1000000] [-OMS 1 | -NMS 29 | -MS]
 //            [-encoder [-fresh] | -gencoder [-fresh]] [-et] [-gpus N] [-seed S]
-//            [-kernel K] [-f32 [-beta B] | -f32q | -BP [-bpstair] | -f16 [-f16all] [-beta B]]
+//            [-kernel K] [-f32 [-beta B] | -f32q | -BP [-bpstair] | -f16 [-f16all] [-f16ep] [-beta B]]
 //
 // Three chains see the same noise (one u per element, the same first_cw and
 // seed scheme): the default draws the quantised int8 LLRs directly
@@ -35,6 +35,9 @@
 // codes (DVB-S2 and like-shaped tables); -f16all (with -f16 only) opens it to
 // every code (ldpc_ctx_set_f16_all_codes: the packed LDS-resident and any-H
 // kernels, -kernel 7 / 1 force them); the JSON line names it ("f16_all_codes").
+// -f16ep (with -f16 only, freely with -f16all) lets the short QC codes run on the
+// edge-parallel binary16 kernel (ldpc_ctx_set_f16_edge_parallel, -kernel 9
+// forces it); the JSON line names it ("f16_edge_parallel").
 //
 // -encoder alone draws 64 codewords once on the host and replicates them over
 // every batch; -encoder -fresh draws new information bits and encodes them on
@@ -68,7 +71,7 @@ struct Opt {
     int iter = 30, fer = 100, batch = 4096, gpus = 1, kernel = LDPC_KERNEL_AUTO;
     long frames = 1 << 20;
     bool encoder = false, gencoder = false, fresh = false, f32 = false, f32q = false, bp = false, bpstair = false;
-    bool f16 = false, f16all = false;
+    bool f16 = false, f16all = false, f16ep = false;
     ldpc_params p{};
     uint64_t seed = 1;
 };
@@ -110,6 +113,7 @@ void worker(int dev, const ldpc_code *h, const Opt &o, double sigma, Totals &tot
     if (o.kernel) CHECK(ldpc_ctx_set_kernel(ctx, o.kernel));
     if (o.bpstair) CHECK(ldpc_ctx_set_bp_staircase(ctx, 1));
     if (o.f16all) CHECK(ldpc_ctx_set_f16_all_codes(ctx, 1));
+    if (o.f16ep) CHECK(ldpc_ctx_set_f16_edge_parallel(ctx, 1));
     void *stream;
     CHECK(ldpc_ctx_stream(ctx, &stream));
     uint32_t table[64];
@@ -225,6 +229,7 @@ int main(int argc, char **argv)
         else if (a == "-f32q") o.f32q = true;
         else if (a == "-f16") o.f16 = true;
         else if (a == "-f16all") o.f16all = true;
+        else if (a == "-f16ep") o.f16ep = true;
         else if (a == "-beta") o.p.beta = (float)atof(nxt());
         else {
             fprintf(stderr, "unknown option %s\n", a.c_str());
@@ -248,6 +253,10 @@ int main(int argc, char **argv)
     }
     if (o.f16all && !o.f16) {
         fprintf(stderr, "usage: -f16all (the binary16 decode on every code) needs -f16\n");
+        return 2;
+    }
+    if (o.f16ep && !o.f16) {
+        fprintf(stderr, "usage: -f16ep (the binary16 decode on the edge-parallel kernel) needs -f16\n");
         return 2;
     }
     if (o.bp) {   // belief propagation: the float chain, whatever -OMS / -NMS / -MS said
@@ -318,9 +327,9 @@ int main(int argc, char **argv)
                eb, ber, fer, (double)fr * k / sec / 1e6, fr, fe, be, fe ? (double)be / fe : 0.0, sec);
         printf("{\"ebn0\": %.3f, \"sigma\": %.6f, \"frames\": %ld, \"frame_errors\": %ld, \"bit_errors\": %ld, "
                "\"ber\": %.6e, \"fer\": %.6e, \"coded_mbps\": %.3f, \"chain\": \"%s\", \"algo\": \"%s\", \"bp_staircase\": %s, "
-               "\"f16_all_codes\": %s}\n",
+               "\"f16_all_codes\": %s, \"f16_edge_parallel\": %s}\n",
                eb, sigma, fr, fe, be, ber, fer, mbps, chain, algo, o.bpstair ? "true" : "false",
-               o.f16all ? "true" : "false");
+               o.f16all ? "true" : "false", o.f16ep ? "true" : "false");
         fflush(stdout);
     }
     ldpc_encoder_destroy(genc);

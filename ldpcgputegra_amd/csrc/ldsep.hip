@@ -42,12 +42,11 @@
 
 #include "kernels.h"
 #include "lds.h"
+#include "ldsep_common.h"   // EP_G, EP_CPP, EP_WAVES (here: codewords per workgroup), kEpShapes, the DPP helpers
 
 namespace {
 
-constexpr int EP_G = 8;                 // lanes per check
-constexpr int EP_CPP = 64 / EP_G;       // checks per pass
-constexpr int EP_WAVES = 4;             // codewords (waves) per workgroup
+using namespace ldsep;
 
 struct EpArgs {
     const float *llr;       // frame-major [batch][N]
@@ -61,11 +60,6 @@ struct EpArgs {
     const uint8_t *cnt_ref;
     int cnt_k;
 };
-
-// lane permutations inside each group of 8 (every lane written: no old value)
-LDPC_DEV uint32_t dpp_xor1(uint32_t x) { return __builtin_amdgcn_mov_dpp((int)x, 0xB1, 0xF, 0xF, true); }
-LDPC_DEV uint32_t dpp_xor2(uint32_t x) { return __builtin_amdgcn_mov_dpp((int)x, 0x4E, 0xF, 0xF, true); }
-LDPC_DEV uint32_t dpp_hmirror(uint32_t x) { return __builtin_amdgcn_mov_dpp((int)x, 0x141, 0xF, 0xF, true); }
 
 template <int NL, int NP, bool NMS>
 __global__ void __launch_bounds__(64 * EP_WAVES) ldsep_decode(EpArgs a)
@@ -178,12 +172,6 @@ __global__ void __launch_bounds__(64 * EP_WAVES) ldsep_decode(EpArgs a)
         }
     }
 }
-
-// (NL, NP) shapes compiled: layers x passes of 8 checks
-struct EpShape {
-    int nl, np;
-};
-constexpr EpShape kEpShapes[] = {{12, 4}, {11, 6}};   // 648x324 (Z = 27), 576x288 (Z = 24)
 
 }  // namespace
 

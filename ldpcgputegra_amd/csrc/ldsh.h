@@ -16,6 +16,14 @@ int ldsh_shape(const ldpc_code *h, const LdsCode &lc, int batch, int *lpp_log2, 
 int launch_ldsh(const LdsCode &lc, const ldpc_code *h, const uint16_t *llr, uint8_t *hard, uint16_t *soft,
                 const DecodeLaunch &L, int lpp_log2, int split, hipStream_t s);
 
+// ldseph (ldseph.hip): the binary16 form of the edge-parallel kernel, family 9 on
+// LdsCode::d_ep_tab, one wave per pair of codewords; behind
+// ldpc_ctx_set_f16_edge_parallel.  Applicable where the float kernel is (the
+// same LDS bytes per wave).  Frame-major in and out, no scratch.
+bool ldseph_applicable(const ldpc_code *h, const LdsCode &lc);
+int launch_ldseph(const LdsCode &lc, const ldpc_code *h, const uint16_t *llr, uint8_t *hard, uint16_t *soft,
+                  const DecodeLaunch &L, hipStream_t s);
+
 // generich: V[node][stride] and msg[edge][stride] binary16 in L.V / L.msg (the
 // messages zeroed by the caller), one lane per pair of codewords.  The stride is
 // the batch rounded up to 128: a wave's piece of a row is one whole run of 64

@@ -54,7 +54,8 @@ def boxplus_host(a, b):
 class Decoder:
     """One C-ABI decoder context (device scratch for ``max_batch`` codewords)."""
 
-    def __init__(self, code, device=0, max_batch=4096, kernel=0, bp_staircase=False, f16_all_codes=False):
+    def __init__(self, code, device=0, max_batch=4096, kernel=0, bp_staircase=False, f16_all_codes=False,
+                 f16_edge_parallel=False):
         self.code = code if isinstance(code, Code) else Code(code)
         self.device = device
         self.max_batch = max_batch
@@ -68,6 +69,8 @@ class Decoder:
             self.set_bp_staircase(True)
         if f16_all_codes:
             self.set_f16_all_codes(True)
+        if f16_edge_parallel:
+            self.set_f16_edge_parallel(True)
 
     # -- configuration
     def set_kernel(self, kernel):
@@ -75,7 +78,8 @@ class Decoder:
         windowed2 (S = 16), 5 = workgroup-cooperative DVB-S2 kernel (coop),
         7 = LDS-resident short-code kernel (int8 and float), 8 = coop3 (slab waves
         doing pre + post, i16 chain; the DVB-S2 r1/2 default), 9 = ldsep
-        (edge-parallel float for short QC codes; the float default where it fits),
+        (edge-parallel float for short QC codes; the float default where it fits;
+        the binary16 decode runs it after set_f16_edge_parallel(True)),
         11 = stairf (float staircase codes, DVB-S2: the float default for them,
         with or without early termination -- with it, one launch per iteration
         plus a syndrome pass, as include/ldpc_mi355x.h states; ALGO_BP runs on it
@@ -122,6 +126,24 @@ class Decoder:
     def f16_all_codes(self):
         on = C.c_int()
         _lib.check(_lib.lib().ldpc_ctx_get_f16_all_codes(self._ctx, C.byref(on)))
+        return bool(on.value)
+
+    def set_f16_edge_parallel(self, flag):
+        """Let the binary16 decode run ldsep (9), the edge-parallel kernel of
+        the short quasi-cyclic codes (648x324, 576x288 and tables of their
+        shape), in binary16: one wave per pair of codewords, one lane per edge.
+        Then the automatic choice of decode_f16_device where the code fits it
+        (``last_kernel`` "ldsep"), and what set_kernel(9) runs; every other
+        setting is decided as without it, whatever f16_all_codes says.  Bit for
+        bit the host decoder's results.  Off (the default) a forced 9 is
+        LDPC_EUNSUPPORTED.  Raises LDPC_EUNSUPPORTED on a host decoder or a
+        code set_kernel(9) refuses (``ldpc_ctx_set_f16_edge_parallel``)."""
+        _lib.check(_lib.lib().ldpc_ctx_set_f16_edge_parallel(self._ctx, int(bool(flag))))
+
+    @property
+    def f16_edge_parallel(self):
+        on = C.c_int()
+        _lib.check(_lib.lib().ldpc_ctx_get_f16_edge_parallel(self._ctx, C.byref(on)))
         return bool(on.value)
 
     def profile(self, enable=True):
