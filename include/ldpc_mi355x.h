@@ -264,6 +264,43 @@ int ldpc_ctx_last_et_stage(ldpc_ctx *ctx, int *first_stage_iters);
  * over more waves) and whether two lanes shared a check (split = 1); 0 / 0
  * when the last decode ran another kernel.  (Introspection for tests.) */
 int ldpc_ctx_last_lds_shape(ldpc_ctx *ctx, int *lanes_per_codeword, int *split);
+/* The edge-parallel float kernel spread over several waves (`ldsepw`, a second
+ * kernel of LDPC_KERNEL_LDSEP; off by default).  LDPC_KERNEL_LDSEP proper puts
+ * one wave on a codeword and holds at most 77 (layer, pass) slots of 8 checks,
+ * which is 648x324 and 576x288.  `ldsepw` puts one workgroup of W = 2 or 4
+ * waves on a codeword, V in the workgroup's LDS, the passes of a layer dealt to
+ * the waves, one workgroup barrier per layer: it takes a table whose layer
+ * plan (ldpc_code_layer_info) has 11 or 12 layers, check degree <= 8 and at
+ * most 24 passes (11 layers) or 12 passes (12 layers) of 8 checks in its widest
+ * layer, and that LDPC_KERNEL_LDSEP proper does not take -- 1944x972, 1248x624
+ * and 2304x1152 among the shipped ones.  Same float contract as
+ * LDPC_KERNEL_LDSEP: bit for bit the serial float decode of the LLRs with
+ * every zero made +0.0.
+ *
+ * ldpc_code_ep_wide_info (no context, no GPU): *n_layers / *n_passes of the
+ * plan, *waves_mask with bit W set for every W compiled for the table (0: the
+ * table does not qualify; then layers and passes are 0 too), *waves_auto the
+ * W the automatic choice launches at `batch`, 0 where the table does not
+ * qualify or the rule -- fitted to measured times, DESIGN.md section 7 --
+ * leaves that batch to the family it ran on before.  Any pointer may be NULL.
+ *
+ * ldpc_ctx_set_ep_wide(ctx, 1): a float min-sum decode (OMS / NMS / MS) of a
+ * qualifying table then accepts ldpc_ctx_set_kernel(ctx, LDPC_KERNEL_LDSEP)
+ * and runs `ldsepw`; LDPC_KERNEL_AUTO runs it where waves_auto != 0;
+ * ldpc_ctx_last_kernel reports LDPC_KERNEL_LDSEP and ldpc_ctx_last_ep_waves
+ * the W launched (0 after any launch that was not `ldsepw`).  The
+ * environment variable LDPC_EPW_WAVES = 2 or 4 forces W whenever `ldsepw`
+ * runs; a W outside the table's mask is LDPC_EUNSUPPORTED before any launch.
+ * LDPC_ALGO_BP, the binary16 and the int8 decodes, and every table that does
+ * not qualify are decided exactly as with the switch off, and with it off
+ * every call behaves as if it did not exist.  Setting it is accepted on any
+ * GPU context (it changes nothing for a table that does not qualify) and
+ * LDPC_EUNSUPPORTED on a host context. */
+int ldpc_code_ep_wide_info(const ldpc_code *h, int batch, int *n_layers, int *n_passes, int *waves_mask,
+                           int *waves_auto);
+int ldpc_ctx_set_ep_wide(ldpc_ctx *ctx, int enable);
+int ldpc_ctx_get_ep_wide(ldpc_ctx *ctx, int *enable);
+int ldpc_ctx_last_ep_waves(ldpc_ctx *ctx, int *waves);
 /* Kernel timing (bench / profiling): when enabled, every decode records HIP
  * events around the decode kernel on the stream it is launched on;
  * ldpc_ctx_kernel_time returns the summed kernel time and launch count since

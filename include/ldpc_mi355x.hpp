@@ -110,6 +110,15 @@ public:
         check(ldpc_ctx_get_f16_edge_parallel(ctx_, &on));
         return on != 0;
     }
+    // the float min-sum decode of the longer QC codes (1944x972, 1248x624, 2304x1152 and tables of their shape) on the
+    // edge-parallel kernel spread over several waves (ldpc_ctx_set_ep_wide; off by default; throws on a host decoder)
+    void setEpWide(bool on) { check(ldpc_ctx_set_ep_wide(ctx_, on ? 1 : 0)); }
+    bool epWide()
+    {
+        int on = 0;
+        check(ldpc_ctx_get_ep_wide(ctx_, &on));
+        return on != 0;
+    }
     ldpc_ctx *context() { return ctx_; }
 
 protected:

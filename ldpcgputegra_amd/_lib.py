@@ -97,6 +97,10 @@ SIGNATURES = {
     "ldpc_ctx_last_skipped": (I, [P, C.POINTER(I)]),
     "ldpc_ctx_last_et_stage": (I, [P, C.POINTER(I)]),
     "ldpc_ctx_last_lds_shape": (I, [P, C.POINTER(I), C.POINTER(I)]),
+    "ldpc_code_ep_wide_info": (I, [P, I, C.POINTER(I), C.POINTER(I), C.POINTER(I), C.POINTER(I)]),
+    "ldpc_ctx_set_ep_wide": (I, [P, I]),
+    "ldpc_ctx_get_ep_wide": (I, [P, C.POINTER(I)]),
+    "ldpc_ctx_last_ep_waves": (I, [P, C.POINTER(I)]),
     "ldpc_ctx_profile": (I, [P, I]),
     "ldpc_ctx_kernel_time": (I, [P, C.POINTER(C.c_double), C.POINTER(I), I]),
     "ldpc_decode_i8": (I, [P, P, P, I, I, C.POINTER(ldpc_params)]),

@@ -189,6 +189,19 @@ class Code:
         _lib.check(_lib.lib().ldpc_code_layer_info(self._h, C.byref(nl), C.byref(w), C.byref(i8), C.byref(f32)))
         return dict(n_layers=nl.value, max_width=w.value, lds_i8=bool(i8.value), lds_f32=bool(f32.value))
 
+    def ep_wide_info(self, batch):
+        """Plan of the edge-parallel float kernel over several waves (``ldsepw``,
+        kernel 9 behind Decoder.set_ep_wide; ``ldpc_code_ep_wide_info``, no GPU):
+        dict(n_layers, n_passes, waves_mask, waves, waves_auto).  ``waves`` lists
+        the W compiled for this table (empty: it does not qualify, and layers and
+        passes are 0); ``waves_auto`` is the W the automatic choice launches at
+        ``batch``, 0 where it leaves the decode to the family it ran on before."""
+        nl, np_, mask, auto = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        _lib.check(_lib.lib().ldpc_code_ep_wide_info(self._h, int(batch), C.byref(nl), C.byref(np_), C.byref(mask),
+                                                     C.byref(auto)))
+        return dict(n_layers=nl.value, n_passes=np_.value, waves_mask=mask.value,
+                    waves=[w for w in range(32) if mask.value >> w & 1], waves_auto=auto.value)
+
     def encode(self, info):
         """DVB-S2 IRA encoding of info bits [batch, K] -> codewords [batch, N]."""
         info = np.ascontiguousarray(info, dtype=np.uint8).reshape(-1, self.k_info)

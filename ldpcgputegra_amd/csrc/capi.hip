@@ -149,7 +149,10 @@ extern "C" int ldpc_ctx_set_kernel(ldpc_ctx *c, int k)
 {
     if (!c || k < LDPC_KERNEL_AUTO || k > LDPC_KERNEL_STAIRF || k == LDPC_KERNEL_HOST)
         return ldpc_set_error(LDPC_EINVAL, "kernel must be 0 (auto) .. 9 or 11");
-    if (!ldpc_ctx_has_kernel(c, k)) return ldpc_set_error(LDPC_EUNSUPPORTED, "kernel %d cannot schedule this code", k);
+    // family 9 also takes the tables of its several-wave kernel once ldpc_ctx_set_ep_wide is on
+    const bool wide = k == LDPC_KERNEL_LDSEP && c->device >= 0 && c->ep_wide && c->lds.epw_valid;
+    if (!ldpc_ctx_has_kernel(c, k) && !wide)
+        return ldpc_set_error(LDPC_EUNSUPPORTED, "kernel %d cannot schedule this code", k);
     c->kernel = k;
     return LDPC_OK;
 }
@@ -199,6 +202,29 @@ extern "C" int ldpc_ctx_get_f16_edge_parallel(ldpc_ctx *c, int *enable)
 {
     if (!c || !enable) return ldpc_set_error(LDPC_EINVAL, "NULL");
     *enable = c->f16_edge_parallel ? 1 : 0;
+    return LDPC_OK;
+}
+
+extern "C" int ldpc_ctx_set_ep_wide(ldpc_ctx *c, int enable)
+{
+    if (!c) return ldpc_set_error(LDPC_EINVAL, "NULL ctx");
+    if (c->device < 0)
+        return ldpc_set_error(LDPC_EUNSUPPORTED, "the edge-parallel float kernel over several waves: host context");
+    c->ep_wide = enable != 0;
+    return LDPC_OK;
+}
+
+extern "C" int ldpc_ctx_get_ep_wide(ldpc_ctx *c, int *enable)
+{
+    if (!c || !enable) return ldpc_set_error(LDPC_EINVAL, "NULL");
+    *enable = c->ep_wide ? 1 : 0;
+    return LDPC_OK;
+}
+
+extern "C" int ldpc_ctx_last_ep_waves(ldpc_ctx *c, int *w)
+{
+    if (!c || !w) return ldpc_set_error(LDPC_EINVAL, "NULL");
+    *w = c->last_ep_waves;
     return LDPC_OK;
 }
 

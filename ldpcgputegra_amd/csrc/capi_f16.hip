@@ -117,6 +117,7 @@ int decode_f16_device(ldpc_ctx *c, Scratch &sc, hipStream_t s, const uint16_t *d
     c->last_skipped = 0;
     c->last_lds_lanes = c->last_lds_split = 0;
     c->last_et_stage = 0;
+    c->last_ep_waves = 0;
     // ldsh and ldseph: frame-major in and out, the whole state in LDS (and registers): no scratch
     const bool resident = kern == LDPC_KERNEL_LDS || kern == LDPC_KERNEL_LDSEP;
     if (kern == LDPC_KERNEL_LDS) {

@@ -58,7 +58,7 @@ bool ldpc_ctx_has_kernel(const ldpc_ctx *c, int k)
 // parameters.  last_skipped records the fastest kernel of this code that the
 // automatic choice could not use for them (algorithm, message / variable
 // ranges), 0 if none
-static int pick_kernel(ldpc_ctx *c, const ldpc_params *p, bool is_float, int stride)
+static int pick_kernel(ldpc_ctx *c, const ldpc_params *p, bool is_float, int stride, int batch)
 {
     c->last_skipped = 0;
     const ldpc_code *h = c->code;
@@ -78,14 +78,21 @@ static int pick_kernel(ldpc_ctx *c, const ldpc_params *p, bool is_float, int str
             c->last_skipped = LDPC_KERNEL_STAIRF;   // no BP there (switch off), or on and the stride too large
         return lds_preferred(h, c->lds, true) ? LDPC_KERNEL_LDS : LDPC_KERNEL_GENERIC;
     }
+    // family 9 on several waves per codeword (ldsepw), min-sum only: only where the one-wave kernel does not fit
+    const bool wide = c->ep_wide && ldsepw_applicable(h, c->lds, is_float);
     switch (c->kernel) {
     case LDPC_KERNEL_LDS: return lds_applicable(h, c->lds, is_float) ? LDPC_KERNEL_LDS : -1;
-    case LDPC_KERNEL_LDSEP: return ldsep_applicable(h, c->lds, is_float) ? LDPC_KERNEL_LDSEP : -1;
+    case LDPC_KERNEL_LDSEP: return ldsep_applicable(h, c->lds, is_float) || wide ? LDPC_KERNEL_LDSEP : -1;
     case LDPC_KERNEL_STAIRF: return (is_float && sf) ? LDPC_KERNEL_STAIRF : -1;
     default: break;
     }
     if (is_float) {
         if (automatic && ldsep_applicable(h, c->lds, true)) return LDPC_KERNEL_LDSEP;
+        if (automatic && wide) {   // where the fitted rule found it faster than the family chosen below
+            bool beats = false;
+            ldsepw_rule(c->lds.epw_nl, c->lds.epw_np, c->lds.epw_mask, batch, &beats);
+            if (beats) return LDPC_KERNEL_LDSEP;
+        }
         if (automatic && sf) return LDPC_KERNEL_STAIRF;
         if (automatic && lds_preferred(h, c->lds, true)) return LDPC_KERNEL_LDS;
         return c->kernel <= LDPC_KERNEL_GENERIC ? LDPC_KERNEL_GENERIC : -1;
@@ -129,9 +136,17 @@ static int select_kernel(ldpc_ctx *c, const DecodeRequest &rq, int *kern)
     if (c->device < 0) return host_only(c);
     if (rq.batch == 0) return LDPC_OK;
     HIP_TRY(hipSetDevice(c->device));
-    const int k = pick_kernel(c, rq.p, rq.is_float, stride_of(rq.batch));
+    const int k = pick_kernel(c, rq.p, rq.is_float, stride_of(rq.batch), rq.batch);
     if (k < 0)
         return ldpc_set_error(LDPC_EUNSUPPORTED, "kernel %d selected but not applicable to these params", c->kernel);
+    int waves = 0;
+    if (k == LDPC_KERNEL_LDSEP && !ldsep_applicable(c->code, c->lds, rq.is_float)) {   // ldsepw: refuse before anything is recorded
+        waves = ldsepw_waves(c->lds, rq.batch);
+        if (!waves)
+            return ldpc_set_error(LDPC_EUNSUPPORTED, "LDPC_EPW_WAVES asks for a number of waves per codeword that is not "
+                                  "compiled for this %dx%d code (mask 0x%x)", c->code->n, c->code->m, c->lds.epw_mask);
+    }
+    c->last_ep_waves = waves;
     c->last_kernel = *kern = k;
     return LDPC_OK;
 }
@@ -274,12 +289,15 @@ static int decode_lds_resident(ldpc_ctx *c, Scratch &sc, hipStream_t s, int kern
     DecodeLaunch L{};
     fill_params(L, rq);
     const bool fuse = rq.ec && kern == LDPC_KERNEL_LDSEP && getenv_int("LDPC_FUSED_COUNT", 1) != 0;
-    if (fuse) {   // ldsep counts in its epilogue (one wave = one codeword)
+    if (fuse) {   // ldsep and ldsepw count in their epilogue (one wave / one workgroup = one codeword)
         L.cnt = rq.ec->counts;
         L.cnt_ref = rq.ec->ref;
         L.cnt_k = rq.ec->k;
     }
     rc = profiled(c, s, &lr, [&] {
+        if (kern == LDPC_KERNEL_LDSEP && c->last_ep_waves)
+            return launch_ldsepw(c->lds, h, (const float *)d_llr, rq.d_hard, (float *)rq.d_soft, batch, rq.n_iter,
+                                 c->last_ep_waves, L, s);
         if (kern == LDPC_KERNEL_LDSEP)
             return launch_ldsep(c->lds, h, (const float *)d_llr, rq.d_hard, (float *)rq.d_soft, batch, rq.n_iter, L, s);
         if (L.algo == LDPC_ALGO_BP)

@@ -11,7 +11,7 @@
 //   ldpc_sim -code dvbs2_r1_2 -min 0.8 -max 1.2 -pas 0.1 -iter 50 -fer 100
 //            [-batch 4096] [-frames 1000000] [-OMS 1 | -NMS 29 | -MS]
 //            [-encoder [-fresh] | -gencoder [-fresh]] [-et] [-gpus N] [-seed S]
-//            [-kernel K] [-f32 [-beta B] | -f32q | -BP [-bpstair] | -f16 [-f16all] [-f16ep] [-beta B]]
+//            [-kernel K] [-f32 [-beta B] [-epwide] | -f32q | -BP [-bpstair] | -f16 [-f16all] [-f16ep] [-beta B]]
 //
 // Three chains see the same noise (one u per element, the same first_cw and
 // seed scheme): the default draws the quantised int8 LLRs directly
@@ -38,6 +38,10 @@
 // -f16ep (with -f16 only, freely with -f16all) lets the short QC codes run on the
 // edge-parallel binary16 kernel (ldpc_ctx_set_f16_edge_parallel, -kernel 9
 // forces it); the JSON line names it ("f16_edge_parallel").
+// -epwide (with -f32 only) lets the float min-sum decode of the longer QC codes
+// (1944x972, 1248x624, 2304x1152) run on the edge-parallel kernel spread over
+// several waves (ldpc_ctx_set_ep_wide, -kernel 9 forces it); the JSON line names
+// it ("ep_wide").
 //
 // -encoder alone draws 64 codewords once on the host and replicates them over
 // every batch; -encoder -fresh draws new information bits and encodes them on
@@ -71,7 +75,7 @@ struct Opt {
     int iter = 30, fer = 100, batch = 4096, gpus = 1, kernel = LDPC_KERNEL_AUTO;
     long frames = 1 << 20;
     bool encoder = false, gencoder = false, fresh = false, f32 = false, f32q = false, bp = false, bpstair = false;
-    bool f16 = false, f16all = false, f16ep = false;
+    bool f16 = false, f16all = false, f16ep = false, epwide = false;
     ldpc_params p{};
     uint64_t seed = 1;
 };
@@ -110,6 +114,7 @@ void worker(int dev, const ldpc_code *h, const Opt &o, double sigma, Totals &tot
     ldpc_ctx *ctx;
     CHECK(ldpc_ctx_create(h, dev, o.batch, &ctx));
     if (genc && o.fresh) CHECK(ldpc_ctx_set_encoder(ctx, genc));
+    if (o.epwide) CHECK(ldpc_ctx_set_ep_wide(ctx, 1));   // first: -kernel 9 takes the longer QC codes only with it on
     if (o.kernel) CHECK(ldpc_ctx_set_kernel(ctx, o.kernel));
     if (o.bpstair) CHECK(ldpc_ctx_set_bp_staircase(ctx, 1));
     if (o.f16all) CHECK(ldpc_ctx_set_f16_all_codes(ctx, 1));
@@ -230,6 +235,7 @@ int main(int argc, char **argv)
         else if (a == "-f16") o.f16 = true;
         else if (a == "-f16all") o.f16all = true;
         else if (a == "-f16ep") o.f16ep = true;
+        else if (a == "-epwide") o.epwide = true;
         else if (a == "-beta") o.p.beta = (float)atof(nxt());
         else {
             fprintf(stderr, "unknown option %s\n", a.c_str());
@@ -257,6 +263,11 @@ int main(int argc, char **argv)
     }
     if (o.f16ep && !o.f16) {
         fprintf(stderr, "usage: -f16ep (the binary16 decode on the edge-parallel kernel) needs -f16\n");
+        return 2;
+    }
+    if (o.epwide && (!o.f32 || o.bp)) {
+        fprintf(stderr, "usage: -epwide (the float min-sum decode on the edge-parallel kernel over several waves) needs "
+                        "-f32 and excludes -BP\n");
         return 2;
     }
     if (o.bp) {   // belief propagation: the float chain, whatever -OMS / -NMS / -MS said
@@ -327,9 +338,9 @@ int main(int argc, char **argv)
                eb, ber, fer, (double)fr * k / sec / 1e6, fr, fe, be, fe ? (double)be / fe : 0.0, sec);
         printf("{\"ebn0\": %.3f, \"sigma\": %.6f, \"frames\": %ld, \"frame_errors\": %ld, \"bit_errors\": %ld, "
                "\"ber\": %.6e, \"fer\": %.6e, \"coded_mbps\": %.3f, \"chain\": \"%s\", \"algo\": \"%s\", \"bp_staircase\": %s, "
-               "\"f16_all_codes\": %s, \"f16_edge_parallel\": %s}\n",
+               "\"f16_all_codes\": %s, \"f16_edge_parallel\": %s, \"ep_wide\": %s}\n",
                eb, sigma, fr, fe, be, ber, fer, mbps, chain, algo, o.bpstair ? "true" : "false",
-               o.f16all ? "true" : "false", o.f16ep ? "true" : "false");
+               o.f16all ? "true" : "false", o.f16ep ? "true" : "false", o.epwide ? "true" : "false");
         fflush(stdout);
     }
     ldpc_encoder_destroy(genc);

@@ -18,6 +18,15 @@ struct LdsCode {
     // edge-parallel float kernel (ldsep.hip): compiled shape, layers, per-slot lane table
     int ep_valid = 0, ep_nl = 0, ep_shape = -1;
     uint32_t *d_ep_tab = nullptr;
+    // the same kernel spread over several waves (ldsepw.hip): layers, passes of 8 checks in the widest layer,
+    // the W compiled for the table (bit W set), per-slot lane table [epw_nl * epw_np][64]
+    int epw_valid = 0, epw_nl = 0, epw_np = 0, epw_mask = 0;
+    uint32_t *d_epw_tab = nullptr;
+};
+
+// host-side plan of ldsepw (no GPU): what ldpc_code_ep_wide_info reports
+struct EpwPlan {
+    int nl = 0, np = 0, mask = 0;   // mask 0: the table does not qualify
 };
 
 int lds_upload(const ldpc_code *h, LdsCode *lc);
@@ -30,6 +39,17 @@ int ldsep_upload(const ldpc_code *h, const std::vector<int4> &layers, LdsCode *l
 bool ldsep_applicable(const ldpc_code *h, const LdsCode &lc, bool is_float);
 int launch_ldsep(const LdsCode &lc, const ldpc_code *h, const float *llr, uint8_t *hard, float *soft, int batch,
                  int iters, const DecodeLaunch &L, hipStream_t s);
+// edge-parallel float kernel over W waves per codeword (ldsepw.hip; kernel 9 behind ldpc_ctx_set_ep_wide)
+EpwPlan ldsepw_plan(const ldpc_code *h, const std::vector<int4> &layers);
+int ldsepw_upload(const ldpc_code *h, const std::vector<int4> &layers, LdsCode *lc);
+bool ldsepw_applicable(const ldpc_code *h, const LdsCode &lc, bool is_float);
+// W the fitted rule launches at `batch` among mask (never 0 for a mask != 0); *beats_old: whether that W was
+// measured faster than the family the table ran on before
+int ldsepw_rule(int nl, int np, int mask, int batch, bool *beats_old);
+// W of this launch: LDPC_EPW_WAVES if set, else the rule's; 0 when the forced W is not compiled for the table
+int ldsepw_waves(const LdsCode &lc, int batch);
+int launch_ldsepw(const LdsCode &lc, const ldpc_code *h, const float *llr, uint8_t *hard, float *soft, int batch,
+                  int iters, int waves, const DecodeLaunch &L, hipStream_t s);
 // reads frame-major llr, writes frame-major hard / soft directly (no interleave);
 // *lanes_per_codeword / *split (either may be null): the shape launched
 int launch_lds(const LdsCode &lc, const ldpc_code *h, const void *llr, uint8_t *hard, void *soft, int batch,

@@ -378,6 +378,27 @@ extern "C" int ldpc_code_layer_info(const ldpc_code *h, int *n_layers, int *max_
     return LDPC_OK;
 }
 
+extern "C" int ldpc_code_ep_wide_info(const ldpc_code *h, int batch, int *n_layers, int *n_passes, int *waves_mask,
+                                      int *waves_auto)
+{
+    if (!h) return ldpc_set_error(LDPC_EINVAL, "NULL code");
+    if (batch < 0) return ldpc_set_error(LDPC_EINVAL, "batch %d < 0", batch);
+    EpwPlan pl;
+    if (h->n <= 65535 && h->e > 0) {   // lds_upload's condition
+        std::vector<int4> layers;
+        int maxw = 0;
+        lds_plan(h, layers, maxw);
+        pl = ldsepw_plan(h, layers);
+    }
+    bool beats = false;
+    const int w = pl.mask ? ldsepw_rule(pl.nl, pl.np, pl.mask, batch, &beats) : 0;
+    if (n_layers) *n_layers = pl.nl;
+    if (n_passes) *n_passes = pl.np;
+    if (waves_mask) *waves_mask = pl.mask;
+    if (waves_auto) *waves_auto = beats ? w : 0;
+    return LDPC_OK;
+}
+
 int lds_upload(const ldpc_code *h, LdsCode *lc)
 {
     *lc = LdsCode{};
@@ -407,7 +428,8 @@ int lds_upload(const ldpc_code *h, LdsCode *lc)
         return ldpc_set_error(LDPC_EDEVICE, "lds table upload");
     }
     lc->valid = 1;
-    return ldsep_upload(h, layers, lc);
+    const int rc = ldsep_upload(h, layers, lc);
+    return rc != LDPC_OK ? rc : ldsepw_upload(h, layers, lc);
 }
 
 void lds_free(LdsCode *lc)
@@ -415,6 +437,7 @@ void lds_free(LdsCode *lc)
     (void)hipFree(lc->d_tab);
     (void)hipFree(lc->d_layers);
     (void)hipFree(lc->d_ep_tab);
+    (void)hipFree(lc->d_epw_tab);
     *lc = LdsCode{};
 }
 

@@ -55,7 +55,7 @@ class Decoder:
     """One C-ABI decoder context (device scratch for ``max_batch`` codewords)."""
 
     def __init__(self, code, device=0, max_batch=4096, kernel=0, bp_staircase=False, f16_all_codes=False,
-                 f16_edge_parallel=False):
+                 f16_edge_parallel=False, ep_wide=False):
         self.code = code if isinstance(code, Code) else Code(code)
         self.device = device
         self.max_batch = max_batch
@@ -63,6 +63,8 @@ class Decoder:
         _lib.check(_lib.lib().ldpc_ctx_create(self.code.handle, device, max_batch, C.byref(h)))
         self._ctx = h
         self._pending = []   # (llr, hard) of queued host-buffer decodes, alive until synchronize()
+        if ep_wide:   # before the kernel: set_kernel(9) takes the longer QC codes only with it on
+            self.set_ep_wide(True)
         if kernel:
             self.set_kernel(kernel)
         if bp_staircase:
@@ -79,7 +81,9 @@ class Decoder:
         7 = LDS-resident short-code kernel (int8 and float), 8 = coop3 (slab waves
         doing pre + post, i16 chain; the DVB-S2 r1/2 default), 9 = ldsep
         (edge-parallel float for short QC codes; the float default where it fits;
-        the binary16 decode runs it after set_f16_edge_parallel(True)),
+        the binary16 decode runs it after set_f16_edge_parallel(True); after
+        set_ep_wide(True) it also takes 1944x972, 1248x624 and 2304x1152, on
+        several waves per codeword),
         11 = stairf (float staircase codes, DVB-S2: the float default for them,
         with or without early termination -- with it, one launch per iteration
         plus a syndrome pass, as include/ldpc_mi355x.h states; ALGO_BP runs on it
@@ -145,6 +149,33 @@ class Decoder:
         on = C.c_int()
         _lib.check(_lib.lib().ldpc_ctx_get_f16_edge_parallel(self._ctx, C.byref(on)))
         return bool(on.value)
+
+    def set_ep_wide(self, flag):
+        """Let the float min-sum decode (MS / OMS / NMS) run ``ldsepw``, the
+        edge-parallel kernel 9 with one codeword spread over 2 or 4 waves, on the
+        quasi-cyclic codes too long for its one-wave form: 1944x972, 1248x624,
+        2304x1152 and tables of their shape (Code.ep_wide_info).  Then
+        set_kernel(9) takes those codes, and the automatic choice runs it where
+        the measured rule says so (``waves_auto`` != 0); ``last_kernel`` is
+        "ldsep" and ``last_ep_waves`` the waves per codeword.  The environment
+        variable LDPC_EPW_WAVES forces 2 or 4.  BP, binary16, int8 and every other
+        code are unaffected.  Off (the default) nothing changes.  Raises
+        LDPC_EUNSUPPORTED on a host decoder (``ldpc_ctx_set_ep_wide``)."""
+        _lib.check(_lib.lib().ldpc_ctx_set_ep_wide(self._ctx, int(bool(flag))))
+
+    @property
+    def ep_wide(self):
+        on = C.c_int()
+        _lib.check(_lib.lib().ldpc_ctx_get_ep_wide(self._ctx, C.byref(on)))
+        return bool(on.value)
+
+    @property
+    def last_ep_waves(self):
+        """Waves per codeword of the last decode's launch if it ran ``ldsepw``
+        (kernel 9 over several waves, set_ep_wide), else 0."""
+        w = C.c_int()
+        _lib.check(_lib.lib().ldpc_ctx_last_ep_waves(self._ctx, C.byref(w)))
+        return w.value
 
     def profile(self, enable=True):
         """Record HIP events around every decode kernel launch."""
