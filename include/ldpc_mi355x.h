@@ -208,7 +208,8 @@ typedef enum ldpc_kernel {
     LDPC_KERNEL_LDS = 7,        /* LDS-resident short-code kernel (whole state in LDS; int8 and float) */
     LDPC_KERNEL_COOP3 = 8,      /* DVB-S2 first-group degree 7: slab waves doing pre + post, i16 chain */
     LDPC_KERNEL_LDSEP = 9,      /* float, short QC codes: one wave per codeword, one lane per edge;
-                                   the automatic choice for float decodes of the codes it fits */
+                                   the automatic choice for float decodes of the codes it fits; binary16
+                                   and int8 after ldpc_ctx_set_f16_edge_parallel / _i8_edge_parallel */
     LDPC_KERNEL_HOST = 10,      /* last_kernel of a device -1 context (the host decoder); not selectable */
     LDPC_KERNEL_STAIRF = 11     /* float, DVB-S2 staircase codes: S consecutive checks of 64/S codewords
                                    per wave, the staircase chain by DPP; the automatic choice for float
@@ -301,6 +302,44 @@ int ldpc_code_ep_wide_info(const ldpc_code *h, int batch, int *n_layers, int *n_
 int ldpc_ctx_set_ep_wide(ldpc_ctx *ctx, int enable);
 int ldpc_ctx_get_ep_wide(ldpc_ctx *ctx, int *enable);
 int ldpc_ctx_last_ep_waves(ldpc_ctx *ctx, int *waves);
+/* The edge-parallel kernel in int8 (`ldsepi`, the int8 element type of
+ * LDPC_KERNEL_LDSEP; off by default).  It takes the tables LDPC_KERNEL_LDSEP
+ * proper takes (802.11n 648x324, 576x288 and tables of their shape), two
+ * codewords per lane as 16-bit halves, one wave per pair, and computes the
+ * reference's fixed-point decode bit for bit: hard decisions, int8 soft output
+ * and iters_used equal those of LDPC_KERNEL_LDS and of the host decoder.
+ *
+ * Its parameter domain is what ldpc_ldsepi_params_ok reports (no context, no
+ * GPU): OMS / NMS / MS, var_max 127, var_min in -127 .. 0, msg_max in
+ * 0 .. 127, offset in 0 .. 255, every NMS factor, early termination on or off.
+ * var_min = -128 is outside it (the var range +-127 that LDPC_KERNEL_COOP and
+ * LDPC_KERNEL_COOP3 also keep to).
+ *
+ * ldpc_ctx_set_i8_edge_parallel(ctx, 1): LDPC_EUNSUPPORTED, with the setting
+ * left as it was, on a host context and on a code for which
+ * ldpc_ctx_set_kernel(ctx, LDPC_KERNEL_LDSEP) fails with ldpc_ctx_set_ep_wide
+ * off (200x100, the DVB-S2 codes, 1944x972 whatever ldpc_ctx_set_ep_wide says).
+ * With it on, an int8 decode (device or host buffers, frame- or node-major) is
+ * decided as follows:
+ *   LDPC_KERNEL_AUTO, parameters inside   LDPC_KERNEL_LDSEP, checked first as for
+ *                                         float32: last_kernel LDPC_KERNEL_LDSEP,
+ *                                         last_skipped 0, last_lds_shape 0 / 0,
+ *                                         last_ep_waves 0;
+ *   LDPC_KERNEL_AUTO, parameters outside  the choice with the switch off
+ *                                         (LDPC_KERNEL_LDS); last_skipped names
+ *                                         LDPC_KERNEL_LDSEP;
+ *   forced 9, parameters inside           `ldsepi`;
+ *   forced 9, parameters outside          LDPC_EUNSUPPORTED, "not applicable";
+ *   every other forced family, float32, binary16, LDPC_ALGO_BP and the mixed
+ *   decoder                               as with the switch off.
+ * The decode allocates no scratch (node-major input: the transpose buffer
+ * LDPC_KERNEL_LDS uses).  The switch is independent of ldpc_ctx_set_ep_wide,
+ * ldpc_ctx_set_f16_edge_parallel and ldpc_ctx_set_f16_all_codes, and with it
+ * off every call behaves as if it did not exist: a forced 9 of an int8 decode
+ * is LDPC_EUNSUPPORTED as before. */
+int ldpc_ctx_set_i8_edge_parallel(ldpc_ctx *ctx, int enable);
+int ldpc_ctx_get_i8_edge_parallel(ldpc_ctx *ctx, int *enable);
+int ldpc_ldsepi_params_ok(const ldpc_params *p, int *ok);
 /* Kernel timing (bench / profiling): when enabled, every decode records HIP
  * events around the decode kernel on the stream it is launched on;
  * ldpc_ctx_kernel_time returns the summed kernel time and launch count since

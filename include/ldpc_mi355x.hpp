@@ -110,6 +110,15 @@ public:
         check(ldpc_ctx_get_f16_edge_parallel(ctx_, &on));
         return on != 0;
     }
+    // the int8 decode on the edge-parallel kernel of the short QC codes (ldpc_ctx_set_i8_edge_parallel; off by
+    // default; throws on a host decoder or a code kernel family 9 cannot schedule)
+    void setI8EdgeParallel(bool on) { check(ldpc_ctx_set_i8_edge_parallel(ctx_, on ? 1 : 0)); }
+    bool i8EdgeParallel()
+    {
+        int on = 0;
+        check(ldpc_ctx_get_i8_edge_parallel(ctx_, &on));
+        return on != 0;
+    }
     // the float min-sum decode of the longer QC codes (1944x972, 1248x624, 2304x1152 and tables of their shape) on the
     // edge-parallel kernel spread over several waves (ldpc_ctx_set_ep_wide; off by default; throws on a host decoder)
     void setEpWide(bool on) { check(ldpc_ctx_set_ep_wide(ctx_, on ? 1 : 0)); }

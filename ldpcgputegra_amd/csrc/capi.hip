@@ -205,6 +205,23 @@ extern "C" int ldpc_ctx_get_f16_edge_parallel(ldpc_ctx *c, int *enable)
     return LDPC_OK;
 }
 
+extern "C" int ldpc_ctx_set_i8_edge_parallel(ldpc_ctx *c, int enable)
+{
+    if (!c) return ldpc_set_error(LDPC_EINVAL, "NULL ctx");
+    if (c->device < 0 || !ldpc_ctx_has_kernel(c, LDPC_KERNEL_LDSEP))
+        return ldpc_set_error(LDPC_EUNSUPPORTED, "the edge-parallel int8 kernel: %s",
+                              c->device < 0 ? "host context" : "the code is not in the shape of kernel family 9");
+    c->i8_edge_parallel = enable != 0;
+    return LDPC_OK;
+}
+
+extern "C" int ldpc_ctx_get_i8_edge_parallel(ldpc_ctx *c, int *enable)
+{
+    if (!c || !enable) return ldpc_set_error(LDPC_EINVAL, "NULL");
+    *enable = c->i8_edge_parallel ? 1 : 0;
+    return LDPC_OK;
+}
+
 extern "C" int ldpc_ctx_set_ep_wide(ldpc_ctx *c, int enable)
 {
     if (!c) return ldpc_set_error(LDPC_EINVAL, "NULL ctx");

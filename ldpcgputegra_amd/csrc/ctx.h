@@ -65,7 +65,8 @@ struct ldpc_ctx {
     bool bp_staircase = false;   // LDPC_ALGO_BP may run on the staircase kernel (ldpc_ctx_set_bp_staircase)
     bool f16_all_codes = false;  // the binary16 decode takes every code: ldsh / generich (ldpc_ctx_set_f16_all_codes)
     bool f16_edge_parallel = false;   // the binary16 decode runs family 9 where it fits: ldseph (ldpc_ctx_set_f16_edge_parallel)
-    bool ep_wide = false;   // float min-sum may run ldsepw, family 9 spread over several waves (ldpc_ctx_set_ep_wide)
+    bool i8_edge_parallel = false;    // the int8 decode runs family 9 where it fits: ldsepi (ldpc_ctx_set_i8_edge_parallel)
+    bool ep_wide = false;  // float min-sum may run ldsepw, family 9 spread over several waves (ldpc_ctx_set_ep_wide)
     int last_ep_waves = 0;  // waves per codeword of the last launch if it was ldsepw, else 0
     int lds_pad = 0;        // extra dynamic LDS per windowed2 workgroup (ldpc_ctx_set_lds_pad)
     hipStream_t stream = nullptr;

@@ -80,9 +80,12 @@ static int pick_kernel(ldpc_ctx *c, const ldpc_params *p, bool is_float, int str
     }
     // family 9 on several waves per codeword (ldsepw), min-sum only: only where the one-wave kernel does not fit
     const bool wide = c->ep_wide && ldsepw_applicable(h, c->lds, is_float);
+    // family 9 in int8 (ldsepi), behind ldpc_ctx_set_i8_edge_parallel: the tables of the one-wave kernel
+    const bool epi = !is_float && c->i8_edge_parallel && ldsepi_applicable(h, c->lds);
     switch (c->kernel) {
     case LDPC_KERNEL_LDS: return lds_applicable(h, c->lds, is_float) ? LDPC_KERNEL_LDS : -1;
-    case LDPC_KERNEL_LDSEP: return ldsep_applicable(h, c->lds, is_float) || wide ? LDPC_KERNEL_LDSEP : -1;
+    case LDPC_KERNEL_LDSEP:
+        return ldsep_applicable(h, c->lds, is_float) || wide || (epi && ldsepi_params_ok(p)) ? LDPC_KERNEL_LDSEP : -1;
     case LDPC_KERNEL_STAIRF: return (is_float && sf) ? LDPC_KERNEL_STAIRF : -1;
     default: break;
     }
@@ -109,6 +112,10 @@ static int pick_kernel(ldpc_ctx *c, const ldpc_params *p, bool is_float, int str
     case LDPC_KERNEL_COOP: return co ? LDPC_KERNEL_COOP : -1;
     case LDPC_KERNEL_COOP3: return co3 ? LDPC_KERNEL_COOP3 : -1;
     default:
+        if (epi) {   // checked first, as for float; outside its domain (var_min = -128) the choice is as before
+            if (ldsepi_params_ok(p)) return LDPC_KERNEL_LDSEP;
+            c->last_skipped = LDPC_KERNEL_LDSEP;
+        }
         if (co3) return LDPC_KERNEL_COOP3;
         if (family_fits(c, LDPC_KERNEL_COOP3)) c->last_skipped = LDPC_KERNEL_COOP3;
         if (co) return LDPC_KERNEL_COOP;
@@ -140,7 +147,8 @@ static int select_kernel(ldpc_ctx *c, const DecodeRequest &rq, int *kern)
     if (k < 0)
         return ldpc_set_error(LDPC_EUNSUPPORTED, "kernel %d selected but not applicable to these params", c->kernel);
     int waves = 0;
-    if (k == LDPC_KERNEL_LDSEP && !ldsep_applicable(c->code, c->lds, rq.is_float)) {   // ldsepw: refuse before anything is recorded
+    // ldsepw (float only: an int8 decode on family 9 is ldsepi, one wave per pair): refuse before anything is recorded
+    if (k == LDPC_KERNEL_LDSEP && rq.is_float && !ldsep_applicable(c->code, c->lds, true)) {
         waves = ldsepw_waves(c->lds, rq.batch);
         if (!waves)
             return ldpc_set_error(LDPC_EUNSUPPORTED, "LDPC_EPW_WAVES asks for a number of waves per codeword that is not "
@@ -280,7 +288,7 @@ static int decode_lds_resident(ldpc_ctx *c, Scratch &sc, hipStream_t s, int kern
     const void *d_llr = rq.d_llr;
     const int batch = rq.batch;
     int rc, lr;
-    if (kern == LDPC_KERNEL_LDS && rq.nm_ld) {   // node-major input: transpose it to frame-major scratch first
+    if (rq.nm_ld) {   // node-major input (int8: family 7 or ldsepi): transpose it to frame-major scratch first
         if ((rc = ensure(&sc.d_msg, &sc.msg_bytes, (size_t)h->n * batch)) != LDPC_OK) return rc;
         if (launch_deinterleave_i8((const int8_t *)d_llr, nullptr, (int8_t *)sc.d_msg, h->n, batch, (int)rq.nm_ld, s))
             return ldpc_set_error(LDPC_EDEVICE, "node-major transpose: %s", hipGetErrorString(hipGetLastError()));
@@ -288,8 +296,9 @@ static int decode_lds_resident(ldpc_ctx *c, Scratch &sc, hipStream_t s, int kern
     }
     DecodeLaunch L{};
     fill_params(L, rq);
-    const bool fuse = rq.ec && kern == LDPC_KERNEL_LDSEP && getenv_int("LDPC_FUSED_COUNT", 1) != 0;
-    if (fuse) {   // ldsep and ldsepw count in their epilogue (one wave / one workgroup = one codeword)
+    const bool fuse = rq.ec && kern == LDPC_KERNEL_LDSEP && rq.is_float && getenv_int("LDPC_FUSED_COUNT", 1) != 0;
+    if (fuse) {   // ldsep and ldsepw count in their epilogue (one wave / one workgroup = one codeword); ldsepi
+                  // (int8, a pair per wave and no barrier) leaves it to the separate count below
         L.cnt = rq.ec->counts;
         L.cnt_ref = rq.ec->ref;
         L.cnt_k = rq.ec->k;
@@ -298,6 +307,8 @@ static int decode_lds_resident(ldpc_ctx *c, Scratch &sc, hipStream_t s, int kern
         if (kern == LDPC_KERNEL_LDSEP && c->last_ep_waves)
             return launch_ldsepw(c->lds, h, (const float *)d_llr, rq.d_hard, (float *)rq.d_soft, batch, rq.n_iter,
                                  c->last_ep_waves, L, s);
+        if (kern == LDPC_KERNEL_LDSEP && !rq.is_float)
+            return launch_ldsepi(c->lds, h, (const int8_t *)d_llr, rq.d_hard, (int8_t *)rq.d_soft, L, s);
         if (kern == LDPC_KERNEL_LDSEP)
             return launch_ldsep(c->lds, h, (const float *)d_llr, rq.d_hard, (float *)rq.d_soft, batch, rq.n_iter, L, s);
         if (L.algo == LDPC_ALGO_BP)

@@ -18,6 +18,10 @@ struct LdsCode {
     // edge-parallel float kernel (ldsep.hip): compiled shape, layers, per-slot lane table
     int ep_valid = 0, ep_nl = 0, ep_shape = -1;
     uint32_t *d_ep_tab = nullptr;
+    // what the int8 form (ldsepi.hip) needs of each layer besides the table: its check degree (4 bits per
+    // layer) and whether it is of a later degree group (bit l)
+    unsigned long long ep_degs = 0;
+    uint32_t ep_later = 0;
     // the same kernel spread over several waves (ldsepw.hip): layers, passes of 8 checks in the widest layer,
     // the W compiled for the table (bit W set), per-slot lane table [epw_nl * epw_np][64]
     int epw_valid = 0, epw_nl = 0, epw_np = 0, epw_mask = 0;
@@ -39,6 +43,12 @@ int ldsep_upload(const ldpc_code *h, const std::vector<int4> &layers, LdsCode *l
 bool ldsep_applicable(const ldpc_code *h, const LdsCode &lc, bool is_float);
 int launch_ldsep(const LdsCode &lc, const ldpc_code *h, const float *llr, uint8_t *hard, float *soft, int batch,
                  int iters, const DecodeLaunch &L, hipStream_t s);
+// its int8 form behind ldpc_ctx_set_i8_edge_parallel (ldsepi.hip): two codewords per lane as i16 halves.
+// Applicable where the float kernel is; ldsepi_params_ok: the parameter domain it takes (var_min >= -127)
+bool ldsepi_applicable(const ldpc_code *h, const LdsCode &lc);
+bool ldsepi_params_ok(const ldpc_params *p);
+int launch_ldsepi(const LdsCode &lc, const ldpc_code *h, const int8_t *llr, uint8_t *hard, int8_t *soft,
+                  const DecodeLaunch &L, hipStream_t s);
 // edge-parallel float kernel over W waves per codeword (ldsepw.hip; kernel 9 behind ldpc_ctx_set_ep_wide)
 EpwPlan ldsepw_plan(const ldpc_code *h, const std::vector<int4> &layers);
 int ldsepw_upload(const ldpc_code *h, const std::vector<int4> &layers, LdsCode *lc);

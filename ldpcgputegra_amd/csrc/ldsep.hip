@@ -210,6 +210,12 @@ int ldsep_upload(const ldpc_code *h, const std::vector<int4> &layers, LdsCode *l
         return ldpc_set_error(LDPC_EDEVICE, "ldsep table upload");
     lc->ep_nl = nl;
     lc->ep_shape = shape;
+    lc->ep_degs = 0;
+    lc->ep_later = 0;
+    for (int l = 0; l < nl; l++) {   // (nl <= 12, degree <= EP_G: 4 bits per layer)
+        lc->ep_degs |= (unsigned long long)layers[l].z << (4 * l);
+        lc->ep_later |= (layers[l].w ? 1u : 0u) << l;
+    }
     lc->ep_valid = 1;
     return LDPC_OK;
 }

@@ -1,5 +1,6 @@
-// ldsep_common.h -- what the two edge-parallel kernels of family 9 share: the
-// float one (ldsep.hip) and its binary16 form (ldseph.hip).  The lane mapping
+// ldsep_common.h -- what the edge-parallel kernels of family 9 share: the
+// float one (ldsep.hip), its binary16 form (ldseph.hip) and its int8 form
+// (ldsepi.hip).  The lane mapping
 // (8 lanes per check, 8 checks per pass), the compiled (layers, passes) shapes
 // that LdsCode::ep_shape indexes, and the lane permutations of the 8-lane
 // butterflies.  The per-slot lane table (LdsCode::d_ep_tab) is built by

@@ -55,7 +55,7 @@ class Decoder:
     """One C-ABI decoder context (device scratch for ``max_batch`` codewords)."""
 
     def __init__(self, code, device=0, max_batch=4096, kernel=0, bp_staircase=False, f16_all_codes=False,
-                 f16_edge_parallel=False, ep_wide=False):
+                 f16_edge_parallel=False, ep_wide=False, i8_edge_parallel=False):
         self.code = code if isinstance(code, Code) else Code(code)
         self.device = device
         self.max_batch = max_batch
@@ -73,6 +73,8 @@ class Decoder:
             self.set_f16_all_codes(True)
         if f16_edge_parallel:
             self.set_f16_edge_parallel(True)
+        if i8_edge_parallel:
+            self.set_i8_edge_parallel(True)
 
     # -- configuration
     def set_kernel(self, kernel):
@@ -81,7 +83,8 @@ class Decoder:
         7 = LDS-resident short-code kernel (int8 and float), 8 = coop3 (slab waves
         doing pre + post, i16 chain; the DVB-S2 r1/2 default), 9 = ldsep
         (edge-parallel float for short QC codes; the float default where it fits;
-        the binary16 decode runs it after set_f16_edge_parallel(True); after
+        the binary16 decode runs it after set_f16_edge_parallel(True), the int8
+        decode after set_i8_edge_parallel(True); after
         set_ep_wide(True) it also takes 1944x972, 1248x624 and 2304x1152, on
         several waves per codeword),
         11 = stairf (float staircase codes, DVB-S2: the float default for them,
@@ -148,6 +151,26 @@ class Decoder:
     def f16_edge_parallel(self):
         on = C.c_int()
         _lib.check(_lib.lib().ldpc_ctx_get_f16_edge_parallel(self._ctx, C.byref(on)))
+        return bool(on.value)
+
+    def set_i8_edge_parallel(self, flag):
+        """Let the int8 decode (decode_i8, decode_i8_device, decode_i8_nm_device)
+        run ldsep (9), the edge-parallel kernel of the short quasi-cyclic codes
+        (648x324, 576x288 and tables of their shape), in int8 (``ldsepi``): one
+        wave per pair of codewords, one lane per edge, bit for bit the reference's
+        fixed-point results.  Then the automatic choice where the parameters are
+        in its domain (var_min >= -127; ``last_kernel`` "ldsep"), and what
+        set_kernel(9) runs; with var_min = -128 the automatic choice stays on 7
+        (``last_skipped`` "ldsep") and a forced 9 is LDPC_EUNSUPPORTED.  Float,
+        binary16, BP and every other forced kernel are unaffected.  Off (the
+        default) nothing changes.  Raises LDPC_EUNSUPPORTED on a host decoder or a
+        code set_kernel(9) refuses without ep_wide (``ldpc_ctx_set_i8_edge_parallel``)."""
+        _lib.check(_lib.lib().ldpc_ctx_set_i8_edge_parallel(self._ctx, int(bool(flag))))
+
+    @property
+    def i8_edge_parallel(self):
+        on = C.c_int()
+        _lib.check(_lib.lib().ldpc_ctx_get_i8_edge_parallel(self._ctx, C.byref(on)))
         return bool(on.value)
 
     def set_ep_wide(self, flag):
