@@ -42,24 +42,29 @@ STREAM = 10            # grid_input draws from streams `stream` and `stream + 1`
 _inputs = {}
 
 
+def table_grid(t, batch, ebn0, step, clip, stream=STREAM):
+    """float32 [batch, N] for the Table t, read-only, not cached: BPSK
+    all-zero-codeword AWGN LLRs 2 y / sigma^2, y = -1 + sigma g, rounded to
+    multiples of `step` and clipped to +-clip * step.  g by Box-Muller in
+    float64 from the splitmix64 streams `stream` and `stream + 1`; sigma =
+    sqrt(1 / (2 R 10^(ebn0 / 10))).  Zeros are +0.0.  The draws are indexed by
+    position, so a smaller batch is a prefix of a larger one."""
+    sigma = math.sqrt(1.0 / (2.0 * (t.k_info / t.n) * 10.0 ** (ebn0 / 10.0)))
+    u1 = (_draw32(batch, t.n, stream).astype(np.float64) + 0.5) / 2.0 ** 32      # in (0, 1): log is finite
+    u2 = _draw32(batch, t.n, stream + 1).astype(np.float64) / 2.0 ** 32
+    g = np.sqrt(-2.0 * np.log(u1)) * np.cos(2.0 * math.pi * u2)
+    llr = 2.0 * (-1.0 + sigma * g) / (sigma * sigma)
+    x = (np.clip(np.rint(llr / step), -clip, clip) * step + 0.0).astype(np.float32)   # + 0.0: rint's -0.0
+    x = np.ascontiguousarray(x)
+    x.setflags(write=False)
+    return x
+
+
 def grid_input(code, batch, ebn0, step, clip, stream=STREAM):
-    """float32 [batch, N], read-only and cached: BPSK all-zero-codeword AWGN
-    LLRs 2 y / sigma^2, y = -1 + sigma g, rounded to multiples of `step` and
-    clipped to +-clip * step.  g by Box-Muller in float64 from the splitmix64
-    streams `stream` and `stream + 1`; sigma = sqrt(1 / (2 R 10^(ebn0 / 10))).
-    Zeros are +0.0."""
+    """table_grid for the shipped table `code`, cached."""
     key = (code, batch, ebn0, step, clip, stream)
     if key not in _inputs:
-        t = load_table(code)
-        sigma = math.sqrt(1.0 / (2.0 * (t.k_info / t.n) * 10.0 ** (ebn0 / 10.0)))
-        u1 = (_draw32(batch, t.n, stream).astype(np.float64) + 0.5) / 2.0 ** 32      # in (0, 1): log is finite
-        u2 = _draw32(batch, t.n, stream + 1).astype(np.float64) / 2.0 ** 32
-        g = np.sqrt(-2.0 * np.log(u1)) * np.cos(2.0 * math.pi * u2)
-        llr = 2.0 * (-1.0 + sigma * g) / (sigma * sigma)
-        x = (np.clip(np.rint(llr / step), -clip, clip) * step + 0.0).astype(np.float32)   # + 0.0: rint's -0.0
-        x = np.ascontiguousarray(x)
-        x.setflags(write=False)
-        _inputs[key] = x
+        _inputs[key] = table_grid(load_table(code), batch, ebn0, step, clip, stream)
     return _inputs[key]
 
 

@@ -21,8 +21,6 @@ grids, so nothing rounds and equality is the tolerance.
 * the fused error count against the separate count kernel;
 * a 648x324 and a 1944x972 decoder used alternately, the latter alternating
   its W and its family."""
-import math
-
 import numpy as np
 import pytest
 
@@ -30,8 +28,8 @@ import float_domain as FD
 import ldsep_domain as ED
 import oracle as O
 import test_ep_wide_cpu as EW
+from float_short_domain import synthetic_input      # the coarse grid at 2 dB for a Table
 from ldpcgputegra_amd import ALGO_BP, ALGO_MS, ALGO_NMS, ALGO_OMS, Code, Decoder, LdpcError, _lib, default_params
-from param_domain import _draw32
 from test_gpu_float_domain import assert_same
 
 pytestmark = pytest.mark.gpu
@@ -64,22 +62,6 @@ def run(dec, x, iters, params, extra=2):
     assert (hard[B:] == HARD_FILL).all() and (soft[B:] == SOFT_FILL).all() and (its[B:] == ITS_FILL).all(), \
         "rows beyond the batch written"
     return hard[:B], soft[:B], its[:B]
-
-
-def synthetic_input(t, key, batch):
-    """float_domain.grid_input's coarse grid for a synthetic table (it takes shipped names only): BPSK all-zero
-    AWGN LLRs at 2 dB rounded to integers and clipped to +-4, from the splitmix64 streams 10 and 11"""
-    if key not in _inputs:
-        step, clip = FD.COARSE
-        sigma = math.sqrt(1.0 / (2.0 * (t.k_info / t.n) * 10.0 ** 0.2))
-        u1 = (_draw32(batch, t.n, FD.STREAM).astype(np.float64) + 0.5) / 2.0 ** 32
-        u2 = _draw32(batch, t.n, FD.STREAM + 1).astype(np.float64) / 2.0 ** 32
-        g = np.sqrt(-2.0 * np.log(u1)) * np.cos(2.0 * math.pi * u2)
-        llr = 2.0 * (-1.0 + sigma * g) / (sigma * sigma)
-        x = np.ascontiguousarray((np.clip(np.rint(llr / step), -clip, clip) * step + 0.0).astype(np.float32))
-        x.setflags(write=False)
-        _inputs[key] = x
-    return _inputs[key]
 
 
 _oracle = {}
