@@ -178,6 +178,16 @@ int ldpc_code_coop3_lc_info(const ldpc_code *h, int *slots, int *max_slots, int 
  * every line unswizzled (plain); 0 / 0 when the code has no coop3 schedule.
  * (Introspection for tests.) */
 int ldpc_code_coop3_lc_banks(const ldpc_code *h, long long *swizzled, long long *plain);
+/* The slots of the coop3 schedule as the kernel's records hold them: windows
+ * per iteration, slots per window (S) and per slab wave, the window of the
+ * tail check, and pt_mask: bit w set where slab wave w holds an inactive slot
+ * in some window other than the tail's (only those waves run the pre's
+ * pass-through selects in steady periods).  active (may be NULL, else room
+ * for max_slots >= n_windows * S bytes): 1 where slot [window][slot] holds a
+ * check.  n_windows = 0 when the code has no coop3 schedule.  (Introspection
+ * for tests.) */
+int ldpc_code_coop3_slots(const ldpc_code *h, int *n_windows, int *S, int *slots_per_wave, int *tail,
+                          unsigned *pt_mask, unsigned char *active, int max_slots);
 /* Layer plan of the LDS-resident kernel (kernel 7): maximal runs of
  * consecutive same-group checks sharing no variable (one block row of a
  * quasi-cyclic code).  lds_i8 / lds_f32: 1 if a codeword's state fits the

@@ -261,6 +261,23 @@ class Code:
         _lib.check(_lib.lib().ldpc_code_coop3_lc_banks(self._h, C.byref(a), C.byref(b)))
         return dict(swizzled=a.value, plain=b.value)
 
+    def coop3_slots(self):
+        """The slots of the coop3 schedule from the kernel's final records:
+        dict(windows, S, slots_per_wave, tail, pt_mask, active) -- active a
+        [windows, S] uint8 array (1: the slot holds a check), pt_mask the slab
+        waves that run the pre's pass-through block in steady periods; None
+        when the code has no coop3 schedule."""
+        L = _lib.lib()
+        v = [C.c_int() for _ in range(4)]
+        m = C.c_uint()
+        _lib.check(L.ldpc_code_coop3_slots(self._h, *[C.byref(x) for x in v], C.byref(m), None, 0))
+        nw, S, spw, tail = (x.value for x in v)
+        if nw == 0:
+            return None
+        act = np.zeros((nw, S), dtype=np.uint8)
+        _lib.check(L.ldpc_code_coop3_slots(self._h, *[C.byref(x) for x in v], C.byref(m), act.ctypes.data, act.size))
+        return dict(windows=nw, S=S, slots_per_wave=spw, tail=tail, pt_mask=m.value, active=act)
+
     def __del__(self):
         h = getattr(self, "_h", None)
         if h is not None and _lib._lib is not None:

@@ -12,6 +12,7 @@ struct CoopCode {
     int n_fwd;       // forwarded info-edge reads per iteration (plan statistic)
     int x0;          // coop3: V row of check 0's x edge (the chain's first input)
     int m0, d1;      // coop3: checks of degree d0 (group 0), degree of the later group
+    uint32_t pt_mask; // coop3: slab waves that can hold an inactive slot outside the tail window (Coop3Host)
     uint32_t *d_tab; // [nw][S][recw]
     // coop3 line cache (LcPlan): slots used, lines resident at a segment start / written back at its end
     int lc_slots, n_lc_pro, n_lc_epi;
@@ -69,6 +70,10 @@ int coop3_upload(const ldpc_code *h, CoopCode *cc);
 struct Coop3Host {
     CoopPlan pl;                 // pl.tab: [nw][S][recw] records as the kernel reads them
     int S = 0, nw = 0, recw = 0, d0 = 0;
+    // bit w: slab wave w (slots w spw .. w spw + spw - 1) holds an inactive slot in some window other than the
+    // tail's: only these waves run the pre's pass-through block in fast periods
+    uint32_t pt_mask = 0;
+    int spw = 0;                 // slots per slab wave
 };
 int coop3_plan_host(const ldpc_code *h, int ws, int r, Coop3Host &o);
 struct LcPlan;

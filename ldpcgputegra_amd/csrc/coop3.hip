@@ -90,6 +90,8 @@ size_t g3_smem(int d0) { return g3_at<SmemOf>(d0); }
 int g3_dist(int d0) { return g3_at<DistOf>(d0); }
 int g3_s(int d0) { return g3_at<SOf>(d0); }
 int g3_xr(int d0) { return g3_at<XrOf>(d0); }
+template <int D> struct SpwOf { static constexpr int v = G3<D>::SPW; };
+int g3_spw(int d0) { return g3_at<SpwOf>(d0); }
 bool g3_degree_ok(int d0) { return d0 == 7 || d0 == 10 || d0 == 14 || d0 == 22 || d0 == 27 || d0 == 30; }
 static_assert(SmemOf<7>::v + 512 <= 160 * 1024 && SmemOf<10>::v + 512 <= 160 * 1024 && SmemOf<14>::v + 512 <= 160 * 1024 &&
                   SmemOf<22>::v + 512 <= 160 * 1024 && SmemOf<27>::v + 512 <= 160 * 1024 &&
@@ -178,7 +180,16 @@ int coop3_plan_host(const ldpc_code *h, int ws, int r, Coop3Host &o)
                 special[(size_t)u * S + k] = 1;
                 special[(size_t)((u + nw - 2) % nw) * S + ((f >> EB) & 63)] = 1;
             }
+    // pt_mask: the slab waves (spw slots each) that get an inactive slot in a
+    // window other than the tail's -- the last one(s), as the inactive slots
+    // come last (r1/2: wave 5 only).  (The inactive slots at the end of slab
+    // wave 1's or 2's range instead, so that a post-first wave with ~400 cycles
+    // of slack keeps the pass-through block: the line-cache plan still fits
+    // 699 of 752 slots, but its modelled bank conflicts rise from 920 to 930 /
+    // 924 extra cycles per iteration: not kept)
+    const int spw = g3_spw(D0);
     std::vector<int> check_at((size_t)nw * S);   // slot -> plan slot (= chain step)
+    uint32_t pt_mask = 0;
     for (int u = 0; u < nw; u++) {
         int n = 0;
         for (int pass = 0; pass < 3; pass++)
@@ -186,6 +197,7 @@ int coop3_plan_host(const ldpc_code *h, int ws, int r, Coop3Host &o)
                 const bool act = k < pl.count[u], sp = special[(size_t)u * S + k] != 0;
                 if ((pass == 0 && sp) || (pass == 1 && act && !sp) || (pass == 2 && !act)) {
                     if (pass == 0 && n >= 8) return 1;   // more than wave 0 holds: no coop3 schedule
+                    if (pass == 2 && u != pl.tail) pt_mask |= 1u << (n / spw);
                     check_at[(size_t)u * S + n] = k;
                     n++;
                 }
@@ -235,7 +247,16 @@ int coop3_plan_host(const ldpc_code *h, int ws, int r, Coop3Host &o)
                         wk[v] = k;
                     }
                 }
+        // and every inactive slot of a window other than the tail's lies in a
+        // slab wave of pt_mask (the others skip the pre's pass-through block)
+        for (int u = 0; u < nw; u++)
+            for (int k = 0; k < S && u != pl.tail; k++)
+                if (!(pl.tab[((size_t)u * S + k) * RECW + D0] & COOP_M_ACT) && !((pt_mask >> (k / spw)) & 1u))
+                    return ldpc_set_error(LDPC_EINVAL, "coop3 plan: inactive slot %d of window %d outside the "
+                                          "pass-through mask 0x%x", k, u, pt_mask);
     }
+    o.pt_mask = pt_mask;
+    o.spw = spw;
     o.S = S;
     o.nw = nw;
     o.recw = RECW;
@@ -323,6 +344,7 @@ int coop3_upload(const ldpc_code *h, CoopCode *cc)
     cc->x0 = (int)h->edge_var[h->check_start[0] + ho.d0 - 2];   // check 0's x edge
     cc->m0 = h->group_cnt[0];
     cc->d1 = h->group_deg[1];
+    cc->pt_mask = ho.pt_mask;
     cc->lc_slots = lp.slots;
     cc->n_lc_pro = (int)lp.pro.size();
     cc->n_lc_epi = (int)lp.epi.size();
@@ -520,6 +542,8 @@ int launch_coop3(const DecodeLaunch &L, const CoopCode &cc, hipStream_t s)
     a.prio = std::min(3, std::max(0, env_int3("LDPC_COOP3_PRIO", coop3_chain_prio(cc.d0))));
     a.mprio = std::min(3, std::max(0, env_int3("LDPC_COOP3_MPRIO", coop3_mem_prio(cc.d0))));
     a.slab_prio = env_int3("LDPC_COOP3_SLAB_PRIO", 2);   // 0 none, 1 static (second waves), 2 fair by phase
+    // LDPC_COOP3_PT_ALL=1 (tests): every slab wave runs the pass-through block, as before the mask
+    a.pt_mask = env_int3("LDPC_COOP3_PT_ALL", 0) != 0 ? 0xFFFFFFFFu : cc.pt_mask;
     const int grid = L.stride / CW;
     a.remap = (grid % 8) == 0 && env_int3("LDPC_COOP3_REMAP", 1) != 0;   // XCD-aware codeword groups
     const bool stamped = env_int3("LDPC_COOP3_STAMP", 0) != 0 && !nms;
@@ -608,6 +632,29 @@ extern "C" int ldpc_code_coop3_lc_banks(const ldpc_code *h, long long *swizzled,
     if (rc < 0) return rc;
     *swizzled = rc == 0 ? lp.bank_extra : 0;
     *plain = rc == 0 ? lp.bank_extra_plain : 0;
+    return LDPC_OK;
+}
+
+// the slots of a code's coop3 schedule, from the final records (tests)
+extern "C" int ldpc_code_coop3_slots(const ldpc_code *h, int *n_windows, int *S, int *slots_per_wave, int *tail,
+                                     unsigned *pt_mask, unsigned char *active, int max_slots)
+{
+    if (!h || !n_windows || !S || !slots_per_wave || !tail || !pt_mask)
+        return ldpc_set_error(LDPC_EINVAL, "coop3 slots args");
+    Coop3Host ho;
+    LcPlan lp;
+    const int rc = coop3_plan_lc(h, ho, lp);
+    if (rc < 0) return rc;
+    *n_windows = rc == 0 ? ho.nw : 0;
+    *S = rc == 0 ? ho.S : 0;
+    *slots_per_wave = rc == 0 ? ho.spw : 0;
+    *tail = rc == 0 ? ho.pl.tail : -1;
+    *pt_mask = rc == 0 ? ho.pt_mask : 0u;
+    if (rc == 0 && active) {
+        if (max_slots < ho.nw * ho.S) return ldpc_set_error(LDPC_EINVAL, "coop3 slots: room for %d", ho.nw * ho.S);
+        for (int i = 0; i < ho.nw * ho.S; i++)
+            active[i] = (ho.pl.tab[(size_t)i * ho.recw + ho.d0] & COOP_M_ACT) ? 1 : 0;
+    }
     return LDPC_OK;
 }
 

@@ -204,6 +204,18 @@ struct G3 {
                                  // edge stage by stage (as the chunked post of degrees >= 10), then packs them
                                  // two per v_perm (PACK2): r08 same box 32.14 -> 31.67 ms
 #endif
+#ifndef LDPC_C3_EPS_MUL
+#define LDPC_C3_EPS_MUL 1        // chain_consts (OMS): eps * m_x as one v_pk_mul_lo_u16 by EPS instead of xor + subtract
+#endif
+#ifndef LDPC_C3_PT_MASK
+#define LDPC_C3_PT_MASK 1        // fast periods: the pre's pass-through block (6 selects) only in the slab waves
+                                 // that can hold an inactive slot (Coop3Args::pt_mask); 0: in every wave
+#endif
+#ifndef LDPC_C3_XD16
+#define LDPC_C3_XD16 0           // experiment switch: the early x pair read as ds_read_u16_d16 / _d16_hi into ONE
+                                 // VGPR, so that no zero-extension is left to redo across the priority branch
+                                 // (census: the pre-first path 1 VALU fewer per period)
+#endif
 template <int WS, int R, int SPW = 8>
 struct Cfg {
     static constexpr int S = SPW * WS;                 // checks per window
@@ -266,6 +278,8 @@ struct Coop3Args {
     uint32_t nmsf;                    // NMS factor per half (value form)
     size_t gstride;                   // bytes between two codeword groups' V
     uint32_t rmm, coff, offp;         // R(msg_max), C(offset) + 255 (R - coff: C form), offset per half (value form)
+    uint32_t pt_mask;                 // bit w: slab wave w holds an inactive (pass-through) slot in some window other
+                                      // than the tail's (Coop3Host::pt_mask; LDPC_COOP3_PT_ALL=1: every wave)
 };
 
 // LEAN (early termination at degree 14: VGPRs): |c| is not kept from pre to
@@ -385,11 +399,27 @@ LDPC_DEV void chain_consts(uint32_t cor, uint32_t mx, uint32_t min1, uint32_t kb
         A = pk_sub(pk_shl5(COV), efm);                            // 32 c_o - eps f m_x
         B = pk_add(A, 0x001F001Fu);
     } else {
-        TV = pk_ashr8(pk_max(pk_sub(pk_min(min1, K.rmm), K.coff), 0u));   // coff = C(off) + 255: C form
+        // coff = C(off) + 255: C form.  min(min1, rmm) is an R magnitude in
+        // [R(0), R(127)], so max(. - coff, 0) is one unsigned saturating subtract
+        TV = pk_ashr8(pk_subu_sat(pk_min(min1, K.rmm), K.coff));
         EPS = EM | 0x00010001u;
+#if LDPC_C3_EPS_MUL
+        // eps * m_x as one v_pk_mul_lo_u16 by EPS (+-1 per half, made anyway)
+        const uint32_t base = pk_sub(COV, pk_mul_lo(pk_ashr8(mx), EPS));   // c_o - eps * m_x
+#else
         const uint32_t base = pk_sub(COV, pk_sub(pk_ashr8(mx) ^ EM, EM));   // c_o - eps * m_x
+#endif
+        // c_o -+ T written between base and its readers: a packed result read
+        // by the very next VALU instruction costs gfx950 a wait state, and with
+        // the pass-through branch closing the block right after these the
+        // compiler, given A and B first, left an s_nop there (census: post-first
+        // path 8 / 7 / 8 s_nop per unrolled period, 7 / 7 / 7 in this order)
+        const uint32_t lo = pk_sub(COV, TV), hi = pk_add(COV, TV);
         A = pk_sub(base, offp);
         B = pk_add(base, offp);
+        L = pk_max(lo, VNEG127);
+        H = pk_min(hi, V127);
+        return;
     }
     L = pk_max(pk_sub(COV, TV), VNEG127);
     H = pk_min(pk_add(COV, TV), V127);
@@ -414,10 +444,11 @@ LDPC_DEV void post_finish(uint32_t xr, uint32_t mx, uint32_t mn1, uint32_t mn2, 
     ax = abs_sat(cx, K.c510);
     const uint32_t sacc = sacc0 ^ cx;
     min2 = pk_max(mn1, pk_min(ax, mn2)), min1 = pk_min(ax, mn1);
+    // (min1 / min2 clipped at rmm: R magnitudes in [R(0), R(127)], pk_subu_sat's domain)
     k1 = NMS ? nms_c(pk_min(min2, K.rmm), fk)
-                            : pk_max(pk_sub(pk_min(min2, K.rmm), K.coff), 0u);   // C(max(min - off, 0))
+                            : pk_subu_sat(pk_min(min2, K.rmm), K.coff);   // C(max(min - off, 0))
     k2 = NMS ? nms_c(pk_min(min1, K.rmm), fk)
-                            : pk_max(pk_sub(pk_min(min1, K.rmm), K.coff), 0u);
+                            : pk_subu_sat(pk_min(min1, K.rmm), K.coff);
     signed_csts(k1, k2, sacc ^ (ODD ? SIGNS : 0u), e1, e2);
 }
 template <int D0, int WS, int R, bool NMS = false, bool LEAN = false, bool KA_ = G3<D0>::KEEP_AD>
@@ -467,6 +498,7 @@ struct Slab3 {
     // past X: c = R(127), no sign, never a minimum), the byte offset of its
     // pair's MB word in an In record
     uint32_t h = 0, hm = 0, mbrd = 0;
+    bool ptw = true;                  // wave-uniform: this slab wave's bit of Coop3Args::pt_mask (pre<.., PTM = true>)
 
     LDPC_DEV const char *lcb() const { return (const char *)&sm.lc[0][0]; }
     LDPC_DEV char *lcw() const { return (char *)&sm.lc[0][0]; }
@@ -535,9 +567,20 @@ struct Slab3 {
     LDPC_DEV uint2 read_x_raw(int g, const St &s) const
     {
         const unsigned short *xs = (const unsigned short *)&sm.xo[g & 1][0][0] + s.xs + 16 * q;
+#if LDPC_C3_XD16
+        u16x2 v;
+        v.x = xs[0];
+        v.y = xs[8];
+        return make_uint2(__builtin_bit_cast(uint32_t, v), 0u);
+#else
         return make_uint2(xs[0], xs[8]);
+#endif
     }
+#if LDPC_C3_XD16
+    LDPC_DEV static uint32_t x_of(uint2 x) { return perm(x.x, x.x, 0x020d000du); }
+#else
     LDPC_DEV static uint32_t x_of(uint2 x) { return perm(x.y, x.x, 0x040d000du); }
+#endif
     LDPC_DEV uint32_t read_x(int g, const St &s) const   // chain inputs of this slot, codewords 2q, 2q+1 -> R pair
     {
         const unsigned short *xs = (const unsigned short *)&sm.xo[g & 1][0][0] + s.xs + 16 * q;
@@ -562,8 +605,9 @@ struct Slab3 {
         sacc ^= sp;
     }
 
-    // pre of window g: chain constants -> cst[g & 1], state -> s
-    template <bool TL, bool FZ_ = false, int MP = -1>
+    // pre of window g: chain constants -> cst[g & 1], state -> s.  PTM (fast
+    // periods): the pass-through block only where this wave's pt_mask bit is set
+    template <bool TL, bool FZ_ = false, int MP = -1, bool PTM = false>
     LDPC_DEV void pre(int g, const In &in, St &s) const
     {
         constexpr bool FZ = FZ_;
@@ -680,10 +724,12 @@ struct Slab3 {
             static_for<0, XL>([&](auto jc) __attribute__((always_inline)) { tail_edge(jc, jc); });
             if constexpr (G::HALF) merge(min1, min2, sacc);   // the other half's info edges
             tail_edge(std::integral_constant<int, XL>{}, std::integral_constant<int, SL>{});   // the last edge
+            // min1 / min2: magnitudes in [R(0), R(127)] (a sink's and the start value R(127) included), so
+            // the difference is in [0, 0x7F00]: non-negative for the signed pk_min that follows
             const uint32_t k1 = NMS ? nms_c(pk_min(min2, K.rmm), fk)
-                                    : pk_min(pk_max(pk_sub(min2, K.coff), 0u), K.rmm) & HIBYTES;
+                                    : pk_min(pk_subu_sat(min2, K.coff), K.rmm) & HIBYTES;
             const uint32_t k2 = NMS ? nms_c(pk_min(min1, K.rmm), fk)
-                                    : pk_min(pk_max(pk_sub(min1, K.coff), 0u), K.rmm) & HIBYTES;
+                                    : pk_min(pk_subu_sat(min1, K.coff), K.rmm) & HIBYTES;
             uint32_t e1, e2, MAn[G::NW];
 #pragma unroll
             for (int i = 0; i < G::NW; i++) MAn[i] = 0;
@@ -711,13 +757,30 @@ struct Slab3 {
             }
             EPS = 0;
         }
-        if (!(meta & COOP_M_ACT)) {   // pass-through slot: Y' = Y (NMS: t = 32 Y + (0, 31))
-            A = COV = 0;
-            B = NMS ? 0x001F001Fu : 0u;
-            EPS = NMS ? 0x00200020u : 0x00010001u;
-            L = VNEG127;
-            H = V127;
-        }
+        // pass-through slot (inactive: the plan fills ~45 of r1/2's 48 slots):
+        // Y' = Y (NMS: t = 32 Y + (0, 31)) -- six selects.  The host puts a
+        // window's inactive slots last, so outside the tail window only the
+        // last slab wave(s) ever hold one: in fast periods (PTM) the waves
+        // outside Coop3Args::pt_mask branch around the block (wave-uniform;
+        // the empty asm keeps the compiler from folding the test into the
+        // selects' condition).  Guarded periods and the tail window run it in
+        // every wave.
+        auto pass_through = [&]() __attribute__((always_inline)) {
+            if (!(meta & COOP_M_ACT)) {
+                A = COV = 0;
+                B = NMS ? 0x001F001Fu : 0u;
+                EPS = NMS ? 0x00200020u : 0x00010001u;
+                L = VNEG127;
+                H = V127;
+            }
+        };
+        if constexpr (PTM && LDPC_C3_PT_MASK) {
+            if (ptw) {
+                asm volatile("");
+                pass_through();
+            }
+        } else
+            pass_through();
         // per codeword records: (A, B), (eps, c_o), (L, H) as i16 pairs (writing
         // the halves with ds_write_b16 / _d16_hi instead of these 6 v_perm ran
         // 3 % slower: 43.7 vs 42.4 ms)
@@ -1712,6 +1775,8 @@ __global__ void __launch_bounds__(64 * (WS + 2)) coop3_decode(Coop3Args a)
         sl.hm = (lane & 1) ? 0xFFFFFFFFu : 0u;
         sl.mbrd = (uint32_t)(((8 + (sq >> 2)) * 8 + skl) * 16 + (sq & 3) * 4);   // record byte 128 + 4 q
     }
+    // wave-uniform (sw comes from the wave index): an SGPR test in the fast periods' pre
+    sl.ptw = ((a.pt_mask >> sw) & 1u) != 0;
     auto next = [&](int &u) __attribute__((always_inline)) { u = (u + 1 == a.nw) ? 0 : u + 1; };
     for (int it = 0;; it++) {   // one segment (ET: one iteration per segment)
         if (STAMP) tseg = stamp3();
@@ -1808,7 +1873,7 @@ __global__ void __launch_bounds__(64 * (WS + 2)) coop3_decode(Coop3Args a)
                 if (LDPC_C3_XEARLY) xe = sl.read_x_raw(p - 1, sp);   // x issued first: it lands with the pre's inputs
                 sl.read_pre((s + 1) % NI, KA ? rcn : sl.read_rec(p + 1), in);
                 if constexpr (KA) rcn = sl.read_rec(p + 2);   // (the next period's pre, either order)
-                sl.template pre<false, ET>(p + 1, in, sn);
+                sl.template pre<false, ET, -1, true>(p + 1, in, sn);
                 if (STAMP) t1 = stampL();
                 if (stag && fair) __builtin_amdgcn_s_setprio(P1);
                 const uint32_t xr = LDPC_C3_XEARLY ? Slab3<D0, WS, R, NMS, LEAN, KA>::x_of(xe) : sl.read_x(p - 1, sp);
@@ -1838,7 +1903,7 @@ __global__ void __launch_bounds__(64 * (WS + 2)) coop3_decode(Coop3Args a)
                 if constexpr (KA) rcn = sl.read_rec(p + 2);
                 if (STAMP) t1 = stampL();
                 if (!SL3::RD16 && fair) __builtin_amdgcn_s_setprio(P1);
-                sl.template pre<false, ET, MP2>(p + 1, in, sn);
+                sl.template pre<false, ET, MP2, true>(p + 1, in, sn);
                 if (STAMP) t3 = stampL();
             } else {
                 if (dpo) {

@@ -53,6 +53,25 @@ LDPC_DEV uint32_t pk_add_sat(uint32_t a, uint32_t b) { return us(__builtin_eleme
 LDPC_DEV uint32_t pk_max(uint32_t a, uint32_t b) { return us(__builtin_elementwise_max(sv(a), sv(b))); }
 LDPC_DEV uint32_t pk_min(uint32_t a, uint32_t b) { return us(__builtin_elementwise_min(sv(a), sv(b))); }
 LDPC_DEV uint32_t pk_sub(uint32_t a, uint32_t b) { return us(sv(a) - sv(b)); }
+// max(a - b, 0) per UNSIGNED half: one v_pk_sub_u16 .. clamp.  It equals the
+// signed pk_max(pk_sub(a, b), 0) wherever both halves of a and of b are in
+// [0, 0x7FFF] (the signed difference then neither wraps nor differs from the
+// unsigned one, and both clamp at 0).  Its users: a = an R-form magnitude in
+// [R(0), R(127)] = [0x00FF, 0x7FFF], b = PkK::coff = C(offset) + 255 with
+// offset in [0, 63] (coop_params_ok; MS: 0), so b <= PK_COFF_MAX
+#ifndef LDPC_C3_SUBU_SAT
+#define LDPC_C3_SUBU_SAT 1   // experiment switch (tools/build_variant.sh): 0 = v_pk_sub_i16 + v_pk_max_i16
+#endif
+constexpr uint32_t PK_COFF_MAX = 63u * 256u + 255u;   // per half
+static_assert(PK_COFF_MAX <= 0x7FFFu, "pk_subu_sat == max(a - b, 0) needs coff's halves non-negative as i16");
+LDPC_DEV uint32_t pk_subu_sat(uint32_t a, uint32_t b)
+{
+#if LDPC_C3_SUBU_SAT
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b)));
+#else
+    return pk_max(pk_sub(a, b), 0u);
+#endif
+}
 LDPC_DEV uint32_t pk_sra15(uint32_t a) { return us(sv(a) >> (short)15); }
 LDPC_DEV uint32_t pk_mul_lo(uint32_t a, uint32_t b)   // v_pk_mul_lo_u16
 {

@@ -44,33 +44,90 @@ def regions(lines):
     yield start, len(lines), cur
 
 
+_ADDR = re.compile(r"//\s*([0-9A-Fa-f]{8,16}):")
+
+
+def _addr(line):
+    m = _ADDR.search(line)
+    return int(m.group(1), 16) if m else None
+
+
+def pass_through_skips(L, mn, s, e):
+    """The wave-uniform branches around the pre's pass-through block inside
+    lines [s, e): {branch line: line of its target} for every conditional
+    forward branch that jumps over at most 16 instructions, all VALU (or the
+    exec save / restore around them), with the block's six selects among them
+    (v_cndmask_b32, or v_mov_b32 under exec).  A slab wave outside the plan's
+    pass-through mask takes the branch; the others fall through."""
+    out = {}
+    for j in range(s, e):
+        if not mn[j].startswith("s_cbranch"):
+            continue
+        a = _addr(L[j])
+        try:
+            off = int(L[j].split()[1], 0)
+        except (IndexError, ValueError):
+            continue
+        if a is None or off <= 0:
+            continue
+        target = a + 4 + 4 * off
+        t = j + 1
+        while t < e and _addr(L[t]) is not None and _addr(L[t]) < target:
+            t += 1
+        span = mn[j + 1:t]
+        if t < e and _addr(L[t]) == target and len(span) <= 16 \
+                and all(m.startswith("v_") or m in ("s_and_saveexec_b64", "s_or_b64") for m in span) \
+                and sum(1 for m in span if m.startswith(("v_cndmask_b32", "v_mov_b32"))) >= 6:
+            out[j] = t
+    return out
+
+
 def coop3_slab_paths(L, mn):
     """The unrolled steady periods of the slab waves (the barrier-delimited
     regions holding all the fast-period variants: > 700 VALU), each split at
     its branches.  The last four large blocks of a region are the post-first
     path (waves 0-2: post + the pre's reads, then the pre) and the pre-first
     path (waves 3-5: reads + pre, then the post); what precedes them is the
-    shared prefix and the guarded tail-window variant."""
+    shared prefix and the guarded tail-window variant.
+
+    A branch around the pre's pass-through block (pass_through_skips) does not
+    split a block: post_first / pre_first count the path of a wave that runs
+    the block (every instruction of the path, as before there was a branch),
+    post_first_skip / pre_first_skip the path of a wave that branches around
+    it, and pt_valu the block's VALU instructions per path."""
     out = []
     start = 0
+    keys = ("valu", "lds", "nop", "waitcnt")
     for i, m in enumerate(mn + ["s_barrier"]):
         if m != "s_barrier":
             continue
         s, e, start = start, i, i + 1
         if sum(1 for x in mn[s:e] if x.startswith("v_")) <= 700:
             continue
-        marks = [s - 1] + [j for j in range(s, e) if mn[j].startswith(("s_cbranch", "s_branch"))] + [e]
+        skips = pass_through_skips(L, mn, s, e)
+        marks = [s - 1] + [j for j in range(s, e)
+                           if mn[j].startswith(("s_cbranch", "s_branch")) and j not in skips] + [e]
         blk = []
         for x, y in zip(marks, marks[1:]):
             c = collections.Counter(classify(m2) for m2 in mn[x + 1:y])
-            blk.append(dict(valu=c["valu"], lds=c["lds"], nop=c["nop"],
-                            waitcnt=sum(1 for m2 in mn[x + 1:y] if m2 == "s_waitcnt")))
+            d = dict(valu=c["valu"], lds=c["lds"], nop=c["nop"],
+                     waitcnt=sum(1 for m2 in mn[x + 1:y] if m2 == "s_waitcnt"))
+            # what a wave taking the block's pass-through branches does not run
+            sk = [m2 for j, t in skips.items() if x < j < y for m2 in mn[j + 1:t]]
+            c = collections.Counter(classify(m2) for m2 in sk)
+            d["skipped"] = dict(valu=c["valu"], lds=c["lds"], nop=c["nop"],
+                                waitcnt=sum(1 for m2 in sk if m2 == "s_waitcnt"))
+            blk.append(d)
         big = [b for b in blk if b["valu"] >= 50]
         if len(big) < 4:
             continue
-        path = lambda bs: {k: sum(b[k] for b in bs) for k in ("valu", "lds", "nop", "waitcnt")}  # noqa: E731
+        path = lambda bs: {k: sum(b[k] for b in bs) for k in keys}  # noqa: E731
+        skip = lambda bs: {k: sum(b[k] - b["skipped"][k] for b in bs) for k in keys}  # noqa: E731
+        ptv = lambda bs: sum(b["skipped"]["valu"] for b in bs)  # noqa: E731
         out.append(dict(lines=[s, e], valu=sum(b["valu"] for b in blk), post_first=path(big[-4:-2]),
-                        pre_first=path(big[-2:])))
+                        pre_first=path(big[-2:]), post_first_skip=skip(big[-4:-2]), pre_first_skip=skip(big[-2:]),
+                        pt_valu=dict(post_first=ptv(big[-4:-2]), pre_first=ptv(big[-2:])),
+                        pass_through_branches=len(skips)))
     return out
 
 
