@@ -219,7 +219,8 @@ typedef enum ldpc_kernel {
     LDPC_KERNEL_COOP3 = 8,      /* DVB-S2 first-group degree 7: slab waves doing pre + post, i16 chain */
     LDPC_KERNEL_LDSEP = 9,      /* float, short QC codes: one wave per codeword, one lane per edge;
                                    the automatic choice for float decodes of the codes it fits; binary16
-                                   and int8 after ldpc_ctx_set_f16_edge_parallel / _i8_edge_parallel */
+                                   and int8 after ldpc_ctx_set_f16_edge_parallel / _i8_edge_parallel; the
+                                   longer QC codes after ldpc_ctx_set_ep_wide (float) / _i8_ep_wide (int8) */
     LDPC_KERNEL_HOST = 10,      /* last_kernel of a device -1 context (the host decoder); not selectable */
     LDPC_KERNEL_STAIRF = 11     /* float, DVB-S2 staircase codes: S consecutive checks of 64/S codewords
                                    per wave, the staircase chain by DPP; the automatic choice for float
@@ -350,6 +351,48 @@ int ldpc_ctx_last_ep_waves(ldpc_ctx *ctx, int *waves);
 int ldpc_ctx_set_i8_edge_parallel(ldpc_ctx *ctx, int enable);
 int ldpc_ctx_get_i8_edge_parallel(ldpc_ctx *ctx, int *enable);
 int ldpc_ldsepi_params_ok(const ldpc_params *p, int *ok);
+/* The int8 edge-parallel kernel spread over several waves (`ldsepwi`, the int8
+ * element type of `ldsepw`; off by default).  It takes the tables `ldsepw`
+ * takes (1944x972, 1248x624, 2304x1152 and tables of their shape): one
+ * workgroup of W = 2 or 4 waves decodes one pair of codewords, each lane
+ * holding the two as 16-bit halves, and computes the reference's fixed-point
+ * decode bit for bit, as `ldsepi` does: hard decisions, int8 soft output and
+ * iters_used equal those of LDPC_KERNEL_LDS and of the host decoder.  Its
+ * parameter domain is ldpc_ldsepi_params_ok's (var_min = -128 is outside).
+ *
+ * ldpc_code_i8_ep_wide_info (no context, no GPU): as ldpc_code_ep_wide_info,
+ * with *waves_mask the W compiled for the table in int8 and *waves_auto the W
+ * the int8 rule launches at `batch`, 0 where the table does not qualify or the
+ * rule -- fitted to measured times, DESIGN.md section 7 -- leaves that batch
+ * to LDPC_KERNEL_LDS.
+ *
+ * ldpc_ctx_set_i8_ep_wide(ctx, 1): LDPC_EUNSUPPORTED, with the setting left as
+ * it was, on a host context and on a code without a several-wave plan
+ * (648x324, 200x100, the DVB-S2 codes).  With it on,
+ * ldpc_ctx_set_kernel(ctx, LDPC_KERNEL_LDSEP) is accepted on the code, and an
+ * int8 decode (device or host buffers, frame- or node-major, with or without
+ * the error counter) is decided as follows:
+ *   LDPC_KERNEL_AUTO, parameters inside,  LDPC_KERNEL_LDSEP: last_kernel
+ *   waves_auto != 0 at this batch         LDPC_KERNEL_LDSEP, last_skipped 0,
+ *                                         last_lds_shape 0 / 0, last_ep_waves W;
+ *   LDPC_KERNEL_AUTO, parameters outside  the choice with the switch off;
+ *                                         last_skipped names LDPC_KERNEL_LDSEP;
+ *   LDPC_KERNEL_AUTO, waves_auto == 0     the choice with the switch off;
+ *   forced 9, parameters inside           `ldsepwi`, whatever the rule says;
+ *   forced 9, parameters outside          LDPC_EUNSUPPORTED, "not applicable";
+ *   every other forced family, float32 (a float decode forced to 9 with only
+ *   this switch on stays "not applicable"), binary16, LDPC_ALGO_BP and the
+ *   mixed decoder                         as with the switch off.
+ * LDPC_EPW_WAVES = 2 or 4 forces W as for `ldsepw`; a W outside the int8 mask
+ * is LDPC_EUNSUPPORTED before any launch.  The decode allocates no scratch
+ * (node-major input: the transpose buffer LDPC_KERNEL_LDS uses).  The switch
+ * is independent of ldpc_ctx_set_ep_wide, ldpc_ctx_set_i8_edge_parallel,
+ * ldpc_ctx_set_f16_edge_parallel and ldpc_ctx_set_f16_all_codes, and with it
+ * off every call behaves as if it did not exist. */
+int ldpc_code_i8_ep_wide_info(const ldpc_code *h, int batch, int *n_layers, int *n_passes, int *waves_mask,
+                              int *waves_auto);
+int ldpc_ctx_set_i8_ep_wide(ldpc_ctx *ctx, int enable);
+int ldpc_ctx_get_i8_ep_wide(ldpc_ctx *ctx, int *enable);
 /* Kernel timing (bench / profiling): when enabled, every decode records HIP
  * events around the decode kernel on the stream it is launched on;
  * ldpc_ctx_kernel_time returns the summed kernel time and launch count since

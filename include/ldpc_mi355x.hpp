@@ -128,6 +128,15 @@ public:
         check(ldpc_ctx_get_ep_wide(ctx_, &on));
         return on != 0;
     }
+    // the int8 decode of those longer QC codes on the edge-parallel kernel spread over several waves
+    // (ldpc_ctx_set_i8_ep_wide; off by default; throws on a host decoder or a code without a several-wave plan)
+    void setI8EpWide(bool on) { check(ldpc_ctx_set_i8_ep_wide(ctx_, on ? 1 : 0)); }
+    bool i8EpWide()
+    {
+        int on = 0;
+        check(ldpc_ctx_get_i8_ep_wide(ctx_, &on));
+        return on != 0;
+    }
     ldpc_ctx *context() { return ctx_; }
 
 protected:

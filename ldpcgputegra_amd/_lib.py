@@ -105,6 +105,9 @@ SIGNATURES = {
     "ldpc_ctx_set_i8_edge_parallel": (I, [P, I]),
     "ldpc_ctx_get_i8_edge_parallel": (I, [P, C.POINTER(I)]),
     "ldpc_ldsepi_params_ok": (I, [C.POINTER(ldpc_params), C.POINTER(I)]),
+    "ldpc_code_i8_ep_wide_info": (I, [P, I, C.POINTER(I), C.POINTER(I), C.POINTER(I), C.POINTER(I)]),
+    "ldpc_ctx_set_i8_ep_wide": (I, [P, I]),
+    "ldpc_ctx_get_i8_ep_wide": (I, [P, C.POINTER(I)]),
     "ldpc_ctx_profile": (I, [P, I]),
     "ldpc_ctx_kernel_time": (I, [P, C.POINTER(C.c_double), C.POINTER(I), I]),
     "ldpc_decode_i8": (I, [P, P, P, I, I, C.POINTER(ldpc_params)]),

@@ -202,6 +202,18 @@ class Code:
         return dict(n_layers=nl.value, n_passes=np_.value, waves_mask=mask.value,
                     waves=[w for w in range(32) if mask.value >> w & 1], waves_auto=auto.value)
 
+    def i8_ep_wide_info(self, batch):
+        """Plan of the edge-parallel int8 kernel over several waves (``ldsepwi``,
+        kernel 9 behind Decoder.set_i8_ep_wide; ``ldpc_code_i8_ep_wide_info``, no
+        GPU): the keys of ep_wide_info, with ``waves`` the W compiled for this
+        table in int8 and ``waves_auto`` the W the int8 rule launches at
+        ``batch``, 0 where it leaves the decode to kernel 7."""
+        nl, np_, mask, auto = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        _lib.check(_lib.lib().ldpc_code_i8_ep_wide_info(self._h, int(batch), C.byref(nl), C.byref(np_), C.byref(mask),
+                                                        C.byref(auto)))
+        return dict(n_layers=nl.value, n_passes=np_.value, waves_mask=mask.value,
+                    waves=[w for w in range(32) if mask.value >> w & 1], waves_auto=auto.value)
+
     def encode(self, info):
         """DVB-S2 IRA encoding of info bits [batch, K] -> codewords [batch, N]."""
         info = np.ascontiguousarray(info, dtype=np.uint8).reshape(-1, self.k_info)

@@ -150,7 +150,8 @@ extern "C" int ldpc_ctx_set_kernel(ldpc_ctx *c, int k)
     if (!c || k < LDPC_KERNEL_AUTO || k > LDPC_KERNEL_STAIRF || k == LDPC_KERNEL_HOST)
         return ldpc_set_error(LDPC_EINVAL, "kernel must be 0 (auto) .. 9 or 11");
     // family 9 also takes the tables of its several-wave kernel once ldpc_ctx_set_ep_wide is on
-    const bool wide = k == LDPC_KERNEL_LDSEP && c->device >= 0 && c->ep_wide && c->lds.epw_valid;
+    // or, for the int8 decode, ldpc_ctx_set_i8_ep_wide
+    const bool wide = k == LDPC_KERNEL_LDSEP && c->device >= 0 && (c->ep_wide || c->i8_ep_wide) && c->lds.epw_valid;
     if (!ldpc_ctx_has_kernel(c, k) && !wide)
         return ldpc_set_error(LDPC_EUNSUPPORTED, "kernel %d cannot schedule this code", k);
     c->kernel = k;
@@ -219,6 +220,23 @@ extern "C" int ldpc_ctx_get_i8_edge_parallel(ldpc_ctx *c, int *enable)
 {
     if (!c || !enable) return ldpc_set_error(LDPC_EINVAL, "NULL");
     *enable = c->i8_edge_parallel ? 1 : 0;
+    return LDPC_OK;
+}
+
+extern "C" int ldpc_ctx_set_i8_ep_wide(ldpc_ctx *c, int enable)
+{
+    if (!c) return ldpc_set_error(LDPC_EINVAL, "NULL ctx");
+    if (c->device < 0 || !ldsepwi_applicable(c->code, c->lds))
+        return ldpc_set_error(LDPC_EUNSUPPORTED, "the edge-parallel int8 kernel over several waves: %s",
+                              c->device < 0 ? "host context" : "the code has no several-wave plan of kernel family 9");
+    c->i8_ep_wide = enable != 0;
+    return LDPC_OK;
+}
+
+extern "C" int ldpc_ctx_get_i8_ep_wide(ldpc_ctx *c, int *enable)
+{
+    if (!c || !enable) return ldpc_set_error(LDPC_EINVAL, "NULL");
+    *enable = c->i8_ep_wide ? 1 : 0;
     return LDPC_OK;
 }
 

@@ -67,7 +67,8 @@ struct ldpc_ctx {
     bool f16_edge_parallel = false;   // the binary16 decode runs family 9 where it fits: ldseph (ldpc_ctx_set_f16_edge_parallel)
     bool i8_edge_parallel = false;    // the int8 decode runs family 9 where it fits: ldsepi (ldpc_ctx_set_i8_edge_parallel)
     bool ep_wide = false;  // float min-sum may run ldsepw, family 9 spread over several waves (ldpc_ctx_set_ep_wide)
-    int last_ep_waves = 0;  // waves per codeword of the last launch if it was ldsepw, else 0
+    bool i8_ep_wide = false;  // the int8 decode may run ldsepwi, family 9 over several waves (ldpc_ctx_set_i8_ep_wide)
+    int last_ep_waves = 0;  // waves per codeword (float) or pair (int8) of the last launch if it was ldsepw / ldsepwi, else 0
     int lds_pad = 0;        // extra dynamic LDS per windowed2 workgroup (ldpc_ctx_set_lds_pad)
     hipStream_t stream = nullptr;
     // device copy of the code

@@ -82,10 +82,14 @@ static int pick_kernel(ldpc_ctx *c, const ldpc_params *p, bool is_float, int str
     const bool wide = c->ep_wide && ldsepw_applicable(h, c->lds, is_float);
     // family 9 in int8 (ldsepi), behind ldpc_ctx_set_i8_edge_parallel: the tables of the one-wave kernel
     const bool epi = !is_float && c->i8_edge_parallel && ldsepi_applicable(h, c->lds);
+    // the same over several waves (ldsepwi), behind ldpc_ctx_set_i8_ep_wide: the tables of ldsepw
+    const bool epwi = !is_float && c->i8_ep_wide && ldsepwi_applicable(h, c->lds);
     switch (c->kernel) {
     case LDPC_KERNEL_LDS: return lds_applicable(h, c->lds, is_float) ? LDPC_KERNEL_LDS : -1;
-    case LDPC_KERNEL_LDSEP:
-        return ldsep_applicable(h, c->lds, is_float) || wide || (epi && ldsepi_params_ok(p)) ? LDPC_KERNEL_LDSEP : -1;
+    case LDPC_KERNEL_LDSEP: {
+        const bool i8 = (epi || epwi) && ldsepi_params_ok(p);
+        return ldsep_applicable(h, c->lds, is_float) || wide || i8 ? LDPC_KERNEL_LDSEP : -1;
+    }
     case LDPC_KERNEL_STAIRF: return (is_float && sf) ? LDPC_KERNEL_STAIRF : -1;
     default: break;
     }
@@ -115,6 +119,15 @@ static int pick_kernel(ldpc_ctx *c, const ldpc_params *p, bool is_float, int str
         if (epi) {   // checked first, as for float; outside its domain (var_min = -128) the choice is as before
             if (ldsepi_params_ok(p)) return LDPC_KERNEL_LDSEP;
             c->last_skipped = LDPC_KERNEL_LDSEP;
+        }
+        if (epwi) {   // inside its domain where the fitted rule found it faster than the family chosen below
+            if (ldsepi_params_ok(p)) {
+                bool beats = false;
+                ldsepwi_rule(c->lds.epw_nl, c->lds.epw_np, ldsepwi_mask(c->lds.epw_nl, c->lds.epw_np), batch, &beats);
+                if (beats) return LDPC_KERNEL_LDSEP;
+            } else {
+                c->last_skipped = LDPC_KERNEL_LDSEP;
+            }
         }
         if (co3) return LDPC_KERNEL_COOP3;
         if (family_fits(c, LDPC_KERNEL_COOP3)) c->last_skipped = LDPC_KERNEL_COOP3;
@@ -147,12 +160,14 @@ static int select_kernel(ldpc_ctx *c, const DecodeRequest &rq, int *kern)
     if (k < 0)
         return ldpc_set_error(LDPC_EUNSUPPORTED, "kernel %d selected but not applicable to these params", c->kernel);
     int waves = 0;
-    // ldsepw (float only: an int8 decode on family 9 is ldsepi, one wave per pair): refuse before anything is recorded
-    if (k == LDPC_KERNEL_LDSEP && rq.is_float && !ldsep_applicable(c->code, c->lds, true)) {
-        waves = ldsepw_waves(c->lds, rq.batch);
+    // ldsepw, or in int8 ldsepwi (on the tables of the one-wave kernel an int8 decode on family 9 is ldsepi, one wave
+    // per pair): refuse before anything is recorded
+    if (k == LDPC_KERNEL_LDSEP && !ldsep_applicable(c->code, c->lds, true)) {
+        waves = rq.is_float ? ldsepw_waves(c->lds, rq.batch) : ldsepwi_waves(c->lds, rq.batch);
         if (!waves)
             return ldpc_set_error(LDPC_EUNSUPPORTED, "LDPC_EPW_WAVES asks for a number of waves per codeword that is not "
-                                  "compiled for this %dx%d code (mask 0x%x)", c->code->n, c->code->m, c->lds.epw_mask);
+                                  "compiled for this %dx%d code (mask 0x%x)", c->code->n, c->code->m,
+                                  rq.is_float ? c->lds.epw_mask : ldsepwi_mask(c->lds.epw_nl, c->lds.epw_np));
     }
     c->last_ep_waves = waves;
     c->last_kernel = *kern = k;
@@ -288,7 +303,7 @@ static int decode_lds_resident(ldpc_ctx *c, Scratch &sc, hipStream_t s, int kern
     const void *d_llr = rq.d_llr;
     const int batch = rq.batch;
     int rc, lr;
-    if (rq.nm_ld) {   // node-major input (int8: family 7 or ldsepi): transpose it to frame-major scratch first
+    if (rq.nm_ld) {   // node-major input (int8: family 7, ldsepi or ldsepwi): transpose it to frame-major scratch first
         if ((rc = ensure(&sc.d_msg, &sc.msg_bytes, (size_t)h->n * batch)) != LDPC_OK) return rc;
         if (launch_deinterleave_i8((const int8_t *)d_llr, nullptr, (int8_t *)sc.d_msg, h->n, batch, (int)rq.nm_ld, s))
             return ldpc_set_error(LDPC_EDEVICE, "node-major transpose: %s", hipGetErrorString(hipGetLastError()));
@@ -298,12 +313,15 @@ static int decode_lds_resident(ldpc_ctx *c, Scratch &sc, hipStream_t s, int kern
     fill_params(L, rq);
     const bool fuse = rq.ec && kern == LDPC_KERNEL_LDSEP && rq.is_float && getenv_int("LDPC_FUSED_COUNT", 1) != 0;
     if (fuse) {   // ldsep and ldsepw count in their epilogue (one wave / one workgroup = one codeword); ldsepi
-                  // (int8, a pair per wave and no barrier) leaves it to the separate count below
+                  // and ldsepwi (int8, a pair per wave / workgroup) leave it to the separate count below
         L.cnt = rq.ec->counts;
         L.cnt_ref = rq.ec->ref;
         L.cnt_k = rq.ec->k;
     }
     rc = profiled(c, s, &lr, [&] {
+        if (kern == LDPC_KERNEL_LDSEP && c->last_ep_waves && !rq.is_float)
+            return launch_ldsepwi(c->lds, h, (const int8_t *)d_llr, rq.d_hard, (int8_t *)rq.d_soft, c->last_ep_waves, L,
+                                  s);
         if (kern == LDPC_KERNEL_LDSEP && c->last_ep_waves)
             return launch_ldsepw(c->lds, h, (const float *)d_llr, rq.d_hard, (float *)rq.d_soft, batch, rq.n_iter,
                                  c->last_ep_waves, L, s);

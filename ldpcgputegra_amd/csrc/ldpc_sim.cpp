@@ -12,7 +12,7 @@
 //            [-batch 4096] [-frames 1000000] [-OMS 1 | -NMS 29 | -MS]
 //            [-encoder [-fresh] | -gencoder [-fresh]] [-et] [-gpus N] [-seed S]
 //            [-kernel K] [-f32 [-beta B] [-epwide] | -f32q | -BP [-bpstair] | -f16 [-f16all] [-f16ep] [-beta B]]
-//            [-i8ep]
+//            [-i8ep] [-i8epw]
 //
 // Three chains see the same noise (one u per element, the same first_cw and
 // seed scheme): the default draws the quantised int8 LLRs directly
@@ -47,6 +47,10 @@
 // or -BP) lets the int8 decode of the short QC codes run on the edge-parallel int8
 // kernel (ldpc_ctx_set_i8_edge_parallel, -kernel 9 forces it); the JSON line names
 // it ("i8_edge_parallel").
+// -i8epw (on the same chains, the same usage errors) lets the int8 decode of the
+// longer QC codes (1944x972, 1248x624, 2304x1152) run on the edge-parallel int8
+// kernel spread over several waves (ldpc_ctx_set_i8_ep_wide, -kernel 9 forces it);
+// the JSON line names it ("i8_ep_wide").
 //
 // -encoder alone draws 64 codewords once on the host and replicates them over
 // every batch; -encoder -fresh draws new information bits and encodes them on
@@ -80,7 +84,7 @@ struct Opt {
     int iter = 30, fer = 100, batch = 4096, gpus = 1, kernel = LDPC_KERNEL_AUTO;
     long frames = 1 << 20;
     bool encoder = false, gencoder = false, fresh = false, f32 = false, f32q = false, bp = false, bpstair = false;
-    bool f16 = false, f16all = false, f16ep = false, epwide = false, i8ep = false;
+    bool f16 = false, f16all = false, f16ep = false, epwide = false, i8ep = false, i8epw = false;
     ldpc_params p{};
     uint64_t seed = 1;
 };
@@ -120,6 +124,7 @@ void worker(int dev, const ldpc_code *h, const Opt &o, double sigma, Totals &tot
     CHECK(ldpc_ctx_create(h, dev, o.batch, &ctx));
     if (genc && o.fresh) CHECK(ldpc_ctx_set_encoder(ctx, genc));
     if (o.epwide) CHECK(ldpc_ctx_set_ep_wide(ctx, 1));   // first: -kernel 9 takes the longer QC codes only with it on
+    if (o.i8epw) CHECK(ldpc_ctx_set_i8_ep_wide(ctx, 1));   // first, for the same reason
     if (o.kernel) CHECK(ldpc_ctx_set_kernel(ctx, o.kernel));
     if (o.bpstair) CHECK(ldpc_ctx_set_bp_staircase(ctx, 1));
     if (o.f16all) CHECK(ldpc_ctx_set_f16_all_codes(ctx, 1));
@@ -243,6 +248,7 @@ int main(int argc, char **argv)
         else if (a == "-f16ep") o.f16ep = true;
         else if (a == "-epwide") o.epwide = true;
         else if (a == "-i8ep") o.i8ep = true;
+        else if (a == "-i8epw") o.i8epw = true;
         else if (a == "-beta") o.p.beta = (float)atof(nxt());
         else {
             fprintf(stderr, "unknown option %s\n", a.c_str());
@@ -280,6 +286,11 @@ int main(int argc, char **argv)
     if (o.i8ep && (o.f32 || o.f16 || o.bp)) {
         fprintf(stderr, "usage: -i8ep (the int8 decode on the edge-parallel kernel) runs on the int8 chains (the "
                         "default and -f32q) and excludes %s\n", o.f32 ? "-f32" : o.f16 ? "-f16" : "-BP");
+        return 2;
+    }
+    if (o.i8epw && (o.f32 || o.f16 || o.bp)) {
+        fprintf(stderr, "usage: -i8epw (the int8 decode on the edge-parallel kernel over several waves) runs on the int8 "
+                        "chains (the default and -f32q) and excludes %s\n", o.f32 ? "-f32" : o.f16 ? "-f16" : "-BP");
         return 2;
     }
     if (o.bp) {   // belief propagation: the float chain, whatever -OMS / -NMS / -MS said
@@ -350,10 +361,11 @@ int main(int argc, char **argv)
                eb, ber, fer, (double)fr * k / sec / 1e6, fr, fe, be, fe ? (double)be / fe : 0.0, sec);
         printf("{\"ebn0\": %.3f, \"sigma\": %.6f, \"frames\": %ld, \"frame_errors\": %ld, \"bit_errors\": %ld, "
                "\"ber\": %.6e, \"fer\": %.6e, \"coded_mbps\": %.3f, \"chain\": \"%s\", \"algo\": \"%s\", \"bp_staircase\": %s, "
-               "\"f16_all_codes\": %s, \"f16_edge_parallel\": %s, \"ep_wide\": %s, \"i8_edge_parallel\": %s}\n",
+               "\"f16_all_codes\": %s, \"f16_edge_parallel\": %s, \"ep_wide\": %s, \"i8_edge_parallel\": %s, "
+               "\"i8_ep_wide\": %s}\n",
                eb, sigma, fr, fe, be, ber, fer, mbps, chain, algo, o.bpstair ? "true" : "false",
                o.f16all ? "true" : "false", o.f16ep ? "true" : "false", o.epwide ? "true" : "false",
-               o.i8ep ? "true" : "false");
+               o.i8ep ? "true" : "false", o.i8epw ? "true" : "false");
         fflush(stdout);
     }
     ldpc_encoder_destroy(genc);

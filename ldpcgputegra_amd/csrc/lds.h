@@ -26,6 +26,9 @@ struct LdsCode {
     // the W compiled for the table (bit W set), per-slot lane table [epw_nl * epw_np][64]
     int epw_valid = 0, epw_nl = 0, epw_np = 0, epw_mask = 0;
     uint32_t *d_epw_tab = nullptr;
+    // what the int8 form of that kernel (ldsepwi.hip) needs besides: as ep_degs / ep_later, of the wide plan's layers
+    unsigned long long epw_degs = 0;
+    uint32_t epw_later = 0;
 };
 
 // host-side plan of ldsepw (no GPU): what ldpc_code_ep_wide_info reports
@@ -60,6 +63,15 @@ int ldsepw_rule(int nl, int np, int mask, int batch, bool *beats_old);
 int ldsepw_waves(const LdsCode &lc, int batch);
 int launch_ldsepw(const LdsCode &lc, const ldpc_code *h, const float *llr, uint8_t *hard, float *soft, int batch,
                   int iters, int waves, const DecodeLaunch &L, hipStream_t s);
+// its int8 form behind ldpc_ctx_set_i8_ep_wide (ldsepwi.hip): one workgroup of W waves per pair of codewords, on
+// ldsepw's plan and table.  ldsepwi_mask: the W compiled for a plan in int8 (bit W set); the parameter domain is
+// ldsepi_params_ok; ldsepwi_rule / ldsepwi_waves as ldsepw_rule / ldsepw_waves, fitted to the int8 measurement
+int ldsepwi_mask(int nl, int np);
+bool ldsepwi_applicable(const ldpc_code *h, const LdsCode &lc);
+int ldsepwi_rule(int nl, int np, int mask, int batch, bool *beats_old);
+int ldsepwi_waves(const LdsCode &lc, int batch);
+int launch_ldsepwi(const LdsCode &lc, const ldpc_code *h, const int8_t *llr, uint8_t *hard, int8_t *soft, int waves,
+                   const DecodeLaunch &L, hipStream_t s);
 // reads frame-major llr, writes frame-major hard / soft directly (no interleave);
 // *lanes_per_codeword / *split (either may be null): the shape launched
 int launch_lds(const LdsCode &lc, const ldpc_code *h, const void *llr, uint8_t *hard, void *soft, int batch,

@@ -399,6 +399,28 @@ extern "C" int ldpc_code_ep_wide_info(const ldpc_code *h, int batch, int *n_laye
     return LDPC_OK;
 }
 
+extern "C" int ldpc_code_i8_ep_wide_info(const ldpc_code *h, int batch, int *n_layers, int *n_passes, int *waves_mask,
+                                         int *waves_auto)
+{
+    if (!h) return ldpc_set_error(LDPC_EINVAL, "NULL code");
+    if (batch < 0) return ldpc_set_error(LDPC_EINVAL, "batch %d < 0", batch);
+    EpwPlan pl;
+    if (h->n <= 65535 && h->e > 0) {   // lds_upload's condition
+        std::vector<int4> layers;
+        int maxw = 0;
+        lds_plan(h, layers, maxw);
+        pl = ldsepw_plan(h, layers);
+    }
+    const int mask = pl.mask ? ldsepwi_mask(pl.nl, pl.np) : 0;   // the int8 shape list's
+    bool beats = false;
+    const int w = mask ? ldsepwi_rule(pl.nl, pl.np, mask, batch, &beats) : 0;
+    if (n_layers) *n_layers = mask ? pl.nl : 0;
+    if (n_passes) *n_passes = mask ? pl.np : 0;
+    if (waves_mask) *waves_mask = mask;
+    if (waves_auto) *waves_auto = beats ? w : 0;
+    return LDPC_OK;
+}
+
 int lds_upload(const ldpc_code *h, LdsCode *lc)
 {
     *lc = LdsCode{};

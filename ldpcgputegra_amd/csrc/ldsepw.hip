@@ -323,6 +323,12 @@ int ldsepw_upload(const ldpc_code *h, const std::vector<int4> &layers, LdsCode *
     lc->epw_nl = pl.nl;
     lc->epw_np = pl.np;
     lc->epw_mask = pl.mask;
+    lc->epw_degs = 0;
+    lc->epw_later = 0;
+    for (int l = 0; l < pl.nl; l++) {   // for ldsepwi.hip, as ldsep_upload's (nl <= 12, degree <= EP_G: 4 bits per layer)
+        lc->epw_degs |= (unsigned long long)layers[l].z << (4 * l);
+        lc->epw_later |= (layers[l].w ? 1u : 0u) << l;
+    }
     lc->epw_valid = 1;
     return LDPC_OK;
 }

@@ -55,7 +55,7 @@ class Decoder:
     """One C-ABI decoder context (device scratch for ``max_batch`` codewords)."""
 
     def __init__(self, code, device=0, max_batch=4096, kernel=0, bp_staircase=False, f16_all_codes=False,
-                 f16_edge_parallel=False, ep_wide=False, i8_edge_parallel=False):
+                 f16_edge_parallel=False, ep_wide=False, i8_edge_parallel=False, i8_ep_wide=False):
         self.code = code if isinstance(code, Code) else Code(code)
         self.device = device
         self.max_batch = max_batch
@@ -65,6 +65,8 @@ class Decoder:
         self._pending = []   # (llr, hard) of queued host-buffer decodes, alive until synchronize()
         if ep_wide:   # before the kernel: set_kernel(9) takes the longer QC codes only with it on
             self.set_ep_wide(True)
+        if i8_ep_wide:   # before the kernel, for the same reason
+            self.set_i8_ep_wide(True)
         if kernel:
             self.set_kernel(kernel)
         if bp_staircase:
@@ -86,7 +88,8 @@ class Decoder:
         the binary16 decode runs it after set_f16_edge_parallel(True), the int8
         decode after set_i8_edge_parallel(True); after
         set_ep_wide(True) it also takes 1944x972, 1248x624 and 2304x1152, on
-        several waves per codeword),
+        several waves per codeword; after set_i8_ep_wide(True) the int8 decode
+        takes them too, on several waves per pair of codewords),
         11 = stairf (float staircase codes, DVB-S2: the float default for them,
         with or without early termination -- with it, one launch per iteration
         plus a syndrome pass, as include/ldpc_mi355x.h states; ALGO_BP runs on it
@@ -192,10 +195,33 @@ class Decoder:
         _lib.check(_lib.lib().ldpc_ctx_get_ep_wide(self._ctx, C.byref(on)))
         return bool(on.value)
 
+    def set_i8_ep_wide(self, flag):
+        """Let the int8 decode (decode_i8, decode_i8_device, decode_i8_nm_device)
+        run ``ldsepwi``, the edge-parallel kernel 9 in int8 with one pair of
+        codewords spread over 2 or 4 waves, on 1944x972, 1248x624, 2304x1152 and
+        tables of their shape (Code.i8_ep_wide_info): bit for bit the reference's
+        fixed-point results.  Then set_kernel(9) takes those codes, and the
+        automatic choice runs it where the parameters are in ``ldsepi``'s domain
+        (var_min >= -127) and the measured rule says so (``waves_auto`` != 0);
+        ``last_kernel`` is "ldsep" and ``last_ep_waves`` the waves per pair.  With
+        var_min = -128 the automatic choice stays on 7 (``last_skipped``
+        "ldsep") and a forced 9 is LDPC_EUNSUPPORTED.  LDPC_EPW_WAVES forces 2
+        or 4.  Float, binary16, BP and every other forced kernel are unaffected.
+        Off (the default) nothing changes.  Raises LDPC_EUNSUPPORTED on a host
+        decoder or a code without a several-wave plan (``ldpc_ctx_set_i8_ep_wide``)."""
+        _lib.check(_lib.lib().ldpc_ctx_set_i8_ep_wide(self._ctx, int(bool(flag))))
+
+    @property
+    def i8_ep_wide(self):
+        on = C.c_int()
+        _lib.check(_lib.lib().ldpc_ctx_get_i8_ep_wide(self._ctx, C.byref(on)))
+        return bool(on.value)
+
     @property
     def last_ep_waves(self):
         """Waves per codeword of the last decode's launch if it ran ``ldsepw``
-        (kernel 9 over several waves, set_ep_wide), else 0."""
+        (kernel 9 over several waves, set_ep_wide), waves per pair of codewords
+        if it ran ``ldsepwi`` (set_i8_ep_wide), else 0."""
         w = C.c_int()
         _lib.check(_lib.lib().ldpc_ctx_last_ep_waves(self._ctx, C.byref(w)))
         return w.value
